@@ -17,7 +17,14 @@ One STEP = one pass of the hot path over the whole genome of the configuration. 
 pass walks a host-side work queue of chromosomes (largest first): generate the chromosome's
 tracks in HBM (NOT timed), then window-index kernel + fused multiplex/reduce kernel over it with
 inputs and outputs resident (timed: synchronise, clock, launch, synchronise, clock).  ms_per_step
-is the sum of the timed sections of one pass; bp/s = covered bp / that time.
+is the sum of the timed sections of one pass; bp/s = covered bp / that time.  On one GPU the passes are
+interleaved per chromosome: its tracks are generated once, then its warm-up and timed launches run back to
+back, each on a fresh track set, and step k is the sum of every chromosome's k-th timed launch.
+
+A plain run does only that and prints the result line.  --full adds everything else the bench measures:
+the end-to-end legs (drop-in layer, whole-genome BigWig files), the CPU baselines and, on the default
+line, the sub-records of the other configurations.  --dump-outputs DIR writes a fixed, seeded sample of
+the last timed step's output runs (and per-chromosome run counts and AUCs) as DIR/<name>.npy.
 
 Multi-GPU (--shard genome, default): ONE genome per step, its chromosomes handed out to the
 ranks by a shared work queue (a counter in the torch.distributed store) -- strong scaling, no
@@ -629,12 +636,14 @@ class Ctx:
         self.use_dist = world > 1       # --force-dist: the collectives also run with a world of ONE rank (RCCL initialised on a 1-GPU box)
 
 
-def measure(ctx, name, ops, N, chrom_ids, mean_run, steps, warmup, scale=1.0, n_set0_arg=-1, f64=False, want_moments=False, values="k8"):
+def measure(ctx, name, ops, N, chrom_ids, mean_run, steps, warmup, scale=1.0, n_set0_arg=-1, f64=False, want_moments=False, values="k8",
+            dump=None):
     """`steps` timed passes of `ops` over the chromosomes `chrom_ids` (GRCh38 lengths x scale), N tracks of mean run
     `mean_run`: the tracks of one chromosome at a time are generated in HBM (untimed), then window index + fused
     multiplex / reduce kernels run with inputs and outputs resident (timed).  Returns the record of this
     configuration on rank 0 (None elsewhere): value, ms_per_step, roofline, bookkeeping.
-    f64: the tracks are handed over as float64 values (what an upstream operator produces): the general kernel."""
+    f64: the tracks are handed over as float64 values (what an upstream operator produces): the general kernel.
+    dump: a dict that receives, per chromosome, a fixed sample of the runs the last timed step wrote (_sample_runs)."""
     import torch
     import torch.distributed as dist
     from wiggletools_amd import engine, synthgen
@@ -671,88 +680,123 @@ def measure(ctx, name, ops, N, chrom_ids, mean_run, steps, warmup, scale=1.0, n_
     moments, stats_last, per_item = {}, {}, {}
     gen_s = [0.0]
 
-    def one_pass(pass_no, record):
-        hot_s = 0.0
-        idx_ms = red_ms = red_call_ms = 0.0
-        for c in my_items(pass_no):
-            t0 = time.perf_counter()
-            seg, s, f, v = synthgen.device_tracks(seed, [chrom_lens[c]], N, mean_run, 0.02, 800, device, chrom_ids=[c])
-            if values in ("full", "fullm"):
-                # every mantissa bit in use, and one value in a million 2^-60 times too small for its window to be summed
-                # exactly: those windows go to the patch kernel (the generator's k/8 values are the friendliest input the
-                # exactness proof can get; this is what less friendly data costs)
-                g = torch.arange(v.numel(), device=v.device, dtype=torch.int64)
-                h = (((g * 2654435761) ^ (g >> 7)) & 0x7FFFFF).to(torch.float32)
-                v = (v + 0.125) * (1.0 + h * (2.0 ** -23))
-                if values == "full":
-                    v[::1000003] *= 2.0 ** -60
-                del g, h
-            if f64:
-                v = v.double()
-            ts = engine.TrackSet.from_device(1, N, seg, s, f, v, np.zeros(N))
-            out = ts.alloc_runs()
-            torch.cuda.synchronize()
-            gen_s[0] += time.perf_counter() - t0
-            ev = [torch.cuda.Event(enable_timing=True) for _ in range(1 + 2 * len(ops))]
-            # ---- timed: inputs resident, outputs resident ----
-            t0 = time.perf_counter()
-            ev[0].record()
-            for j, op in enumerate(ops):
-                if j == 0:
-                    ts.index(op, stream)        # reducers of one item share the window index (same window width)
-                ev[1 + 2 * j].record()
-                ts.reduce(op, out, n_set0=n_set0, stream=stream, sync=False)
-                ev[2 + 2 * j].record()
-                # THE KERNEL'S duration: the library's own HIP events, recorded on the launch stream immediately before and after the
-                # launch (csrc/wt_engine.hip ev_r0 / ev_r1: behind the memsets of the look-back words, around the kernel and -- when
-                # windows are patched -- its patch kernels); reading them waits for this launch.  The events of THIS file around the
-                # whole call also see the three memsets and the host's way from the record to the launch (Python, ctypes, plan, four
-                # API calls) while the stream stands still: 0.1-0.3 ms per launch, 5-10 % of C2's kernels (round 6:
-                # tools/experiments/r6_launch_gap.sh -- rocprofv3's kernel durations agree with the library's events).
-                st_j = ts.stats()
-                red_ms += st_j["reduce_ms"]
-                if j == 0:
-                    idx_ms += st_j["index_ms"]
-            torch.cuda.synchronize()
-            dt = time.perf_counter() - t0
-            # ---- untimed bookkeeping ----
-            hot_s += dt
-            for j in range(len(ops)):
-                red_call_ms += ev[1 + 2 * j].elapsed_time(ev[2 + 2 * j])
-            if record:
-                n_runs = ts.reduce(ops[-1], out, n_set0=n_set0, stream=stream, sync=True)
-                st = ts.stats()
-                agg["bp"] += st["covered_bp"]; agg["runs"] += n_runs; agg["intervals"] += int(seg[-1])
-                agg["windows"] += st["n_windows"] * len(ops)
-                agg["auc"] += out.auc()
-                stats_last.update(st)
-                agg["patched"] = agg.get("patched", 0) + st.get("patched_windows", 0)
-                per_item[c] = dt * 1e3
-                if want_moments or use_dist:
-                    # Pearson moments of tracks 0 and 1 of this chromosome (scalar gather readiness)
-                    a, b = int(seg[0]), int(seg[2])
-                    ts2 = engine.TrackSet.from_device(1, 2, seg[:3] - seg[0], s[a:b], f[a:b], v[a:b].float() if f64 else v[a:b], np.zeros(2))
-                    moments[c] = ts2.pearson_moments()
-                    ts2.close()
-            ts.close()
-            del ts, out, s, f, v
-        return hot_s, idx_ms, red_ms, red_call_ms
+    def generate(c):
+        """The tracks of chromosome c in HBM (untimed): (seg, start, finish, value)."""
+        t0 = time.perf_counter()
+        seg, s, f, v = synthgen.device_tracks(seed, [chrom_lens[c]], N, mean_run, 0.02, 800, device, chrom_ids=[c])
+        if values in ("full", "fullm"):
+            # every mantissa bit in use, and one value in a million 2^-60 times too small for its window to be summed
+            # exactly: those windows go to the patch kernel (the generator's k/8 values are the friendliest input the
+            # exactness proof can get; this is what less friendly data costs)
+            g = torch.arange(v.numel(), device=v.device, dtype=torch.int64)
+            h = (((g * 2654435761) ^ (g >> 7)) & 0x7FFFFF).to(torch.float32)
+            v = (v + 0.125) * (1.0 + h * (2.0 ** -23))
+            if values == "full":
+                v[::1000003] *= 2.0 ** -60
+            del g, h
+        if f64:
+            v = v.double()
+        torch.cuda.synchronize()
+        gen_s[0] += time.perf_counter() - t0
+        return seg, s, f, v
 
-    for w in range(max(warmup, 0)):
-        one_pass(-1 - w, False)
+    def one_item(c, tracks, record):
+        """One timed launch sequence (window index + reducers) over chromosome c on a fresh track set; returns
+        (seconds, index ms, reduce ms, reduce-call ms).  `record`: the step whose figures (and outputs) are kept."""
+        seg, s, f, v = tracks
+        t0 = time.perf_counter()
+        ts = engine.TrackSet.from_device(1, N, seg, s, f, v, np.zeros(N))
+        out = ts.alloc_runs()
+        torch.cuda.synchronize()
+        gen_s[0] += time.perf_counter() - t0
+        idx_ms = red_ms = red_call_ms = 0.0
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(1 + 2 * len(ops))]
+        # ---- timed: inputs resident, outputs resident ----
+        t0 = time.perf_counter()
+        ev[0].record()
+        for j, op in enumerate(ops):
+            if j == 0:
+                ts.index(op, stream)        # reducers of one item share the window index (same window width)
+            ev[1 + 2 * j].record()
+            ts.reduce(op, out, n_set0=n_set0, stream=stream, sync=False)
+            ev[2 + 2 * j].record()
+            # THE KERNEL'S duration: the library's own HIP events, recorded on the launch stream immediately before and after the
+            # launch (csrc/wt_engine.hip ev_r0 / ev_r1: behind the memsets of the look-back words, around the kernel and -- when
+            # windows are patched -- its patch kernels); reading them waits for this launch.  The events of THIS file around the
+            # whole call also see the three memsets and the host's way from the record to the launch (Python, ctypes, plan, four
+            # API calls) while the stream stands still: 0.1-0.3 ms per launch, 5-10 % of C2's kernels (round 6:
+            # tools/experiments/r6_launch_gap.sh -- rocprofv3's kernel durations agree with the library's events).
+            st_j = ts.stats()
+            red_ms += st_j["reduce_ms"]
+            if j == 0:
+                idx_ms += st_j["index_ms"]
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        # ---- untimed bookkeeping ----
+        for j in range(len(ops)):
+            red_call_ms += ev[1 + 2 * j].elapsed_time(ev[2 + 2 * j])
+        if record:
+            n_runs = ts.reduce(ops[-1], out, n_set0=n_set0, stream=stream, sync=True)
+            st = ts.stats()
+            auc = out.auc()
+            agg["bp"] += st["covered_bp"]; agg["runs"] += n_runs; agg["intervals"] += int(seg[-1])
+            agg["windows"] += st["n_windows"] * len(ops)
+            agg["auc"] += auc
+            stats_last.update(st)
+            agg["patched"] = agg.get("patched", 0) + st.get("patched_windows", 0)
+            per_item[c] = dt * 1e3
+            if want_moments or use_dist:
+                # Pearson moments of tracks 0 and 1 of this chromosome (scalar gather readiness)
+                a, b = int(seg[0]), int(seg[2])
+                ts2 = engine.TrackSet.from_device(1, 2, seg[:3] - seg[0], s[a:b], f[a:b], v[a:b].float() if f64 else v[a:b], np.zeros(2))
+                moments[c] = ts2.pearson_moments()
+                ts2.close()
+            if dump is not None:
+                dump[c] = _sample_runs(out, n_runs, c, max(1, int(round(DUMP_RUNS * chrom_lens[c] / genome_bp))), auc, moments.get(c))
+        ts.close()
+        del ts, out
+        return dt, idx_ms, red_ms, red_call_ms
 
     pass_s, idx_tot, red_tot, red_call_tot = [], 0.0, 0.0, 0.0
-    for k in range(steps):
-        if use_dist:
+    if use_dist:
+        # several ranks: pass after pass, every pass a fresh work queue; a chromosome's tracks are generated for every launch
+        def one_pass(pass_no, record):
+            tot = [0.0, 0.0, 0.0, 0.0]
+            for c in my_items(pass_no):
+                tot = [x + y for x, y in zip(tot, one_item(c, generate(c), record))]
+            return tot
+
+        for w in range(max(warmup, 0)):
+            one_pass(-1 - w, False)
+        for k in range(steps):
             dist.barrier()
-        torch.cuda.synchronize()
-        hs, im, rm, rcm = one_pass(k, k == steps - 1)
-        t = torch.tensor([hs], dtype=torch.float64, device=ctx.cdev)
-        if use_dist:
+            torch.cuda.synchronize()
+            hs, im, rm, rcm = one_pass(k, k == steps - 1)
+            t = torch.tensor([hs], dtype=torch.float64, device=ctx.cdev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)        # a pass is over when the slowest rank is
             dist.barrier()
-        pass_s.append(float(t.item()))
-        idx_tot += im; red_tot += rm; red_call_tot += rcm
+            pass_s.append(float(t.item()))
+            idx_tot += im; red_tot += rm; red_call_tot += rcm
+        if dump is not None and not replicas:
+            parts = [None] * world
+            dist.all_gather_object(parts, dict(dump))      # every chromosome was sampled by exactly one rank
+            for p in parts:
+                dump.update(p)
+    else:
+        # one GPU: chromosome after chromosome, its tracks generated ONCE and its warm-up and timed launches run back to back;
+        # step k's time is the sum over chromosomes of their k-th timed launch -- the same launches on the same inputs as
+        # pass after pass, without regenerating 233 GB of run lists for every pass
+        per_step = [[0.0, 0.0, 0.0, 0.0] for _ in range(steps)]
+        for c in my_items(0):
+            tracks = generate(c)
+            for w in range(max(warmup, 0)):
+                one_item(c, tracks, False)
+            for k in range(steps):
+                per_step[k] = [x + y for x, y in zip(per_step[k], one_item(c, tracks, k == steps - 1))]
+            del tracks
+        for hs, im, rm, rcm in per_step:
+            pass_s.append(hs)
+            idx_tot += im; red_tot += rm; red_call_tot += rcm
     elapsed = float(sum(pass_s))
 
     # genome-wide scalars (RCCL over xGMI when world > 1): sums by all_reduce, Pearson by all_gather + ordered merge
@@ -887,6 +931,42 @@ def measure(ctx, name, ops, N, chrom_ids, mean_run, steps, warmup, scale=1.0, n_
         "gen_seconds_total": gen_all, "pass_seconds": pass_s,
         "_chrom_lens": [chrom_lens[c] for c in chrom_ids],
     }
+
+
+DUMP_RUNS = 1 << 20        # output runs sampled per step for --dump-outputs (4 float64 arrays: 32 MB)
+
+
+def _sample_runs(out, n_runs, c, k, auc, moments):
+    """A fixed sample of one chromosome's output runs: k run indices drawn without replacement from a generator seeded by
+    (SEED, chromosome), in order -- every run when there are no more than k."""
+    import torch
+    if n_runs <= k:
+        idx = np.arange(n_runs, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng([SEED, c]).choice(n_runs, size=k, replace=False)).astype(np.int64)
+    it = torch.from_numpy(idx).to(out.start.device)
+    return {"start": out.start[it].cpu().numpy(), "finish": out.finish[it].cpu().numpy(), "value": out.value[it].cpu().numpy(),
+            "n_runs": n_runs, "auc": auc, "moments": moments}
+
+
+def write_outputs(path, dump):
+    """--dump-outputs: the sampled output runs of the last timed step (chromosomes in index order) and the per-chromosome
+    figures, every array float64 (coordinates are below 2^31: exact)."""
+    os.makedirs(path, exist_ok=True)
+    cs = sorted(dump)
+    arrays = {
+        "runs_chrom": np.concatenate([np.full(len(dump[c]["start"]), c, np.float64) for c in cs]),
+        "runs_start": np.concatenate([dump[c]["start"].astype(np.float64) for c in cs]),
+        "runs_finish": np.concatenate([dump[c]["finish"].astype(np.float64) for c in cs]),
+        "runs_value": np.concatenate([dump[c]["value"].astype(np.float64) for c in cs]),
+        "chrom_index": np.array(cs, np.float64),
+        "chrom_output_runs": np.array([dump[c]["n_runs"] for c in cs], np.float64),
+        "chrom_auc": np.array([dump[c]["auc"] for c in cs], np.float64),
+    }
+    if cs and all(dump[c]["moments"] is not None for c in cs):
+        arrays["chrom_pearson_moments_tracks_0_1"] = np.array([dump[c]["moments"] for c in cs], np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def with_cpu(res, chrom_ids, ops, N, mean_run, many_core, target_s=12.0):
@@ -1027,6 +1107,12 @@ def main():
     ap.add_argument("--e2e-mbp", type=float, default=248.956422, help="chromosome length of the end-to-end (drop-in layer) leg; default chromosome 1")
     ap.add_argument("--no-genome-files", action="store_true", help="skip the whole-genome BigWig-files-to-result leg (e2e_bigwig_genome)")
     ap.add_argument("--chr1-files", action="store_true", help="also run round 3's one-chromosome file leg (e2e_bigwig: chromosome 1 x N files)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: the end-to-end and file legs, the CPU baselines and the sub-records "
+                         "of the other configurations (the --no-* options above switch parts of it off)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write a fixed sample of the output runs of the last step and per-chromosome "
+                         "figures as DIR/<name>.npy (float64)")
     args = ap.parse_args()
 
     import torch
@@ -1071,16 +1157,19 @@ def main():
     N = args.tracks if args.tracks else cfg["tracks"]
     chrom_ids = cfg["chroms"] if not args.chroms else [int(x) for x in args.chroms.split(",")]
     t_start = time.perf_counter()
+    dump = {} if args.dump_outputs else None
     res = measure(ctx, args.config, ops, N, chrom_ids, args.mean_run, args.steps, args.warmup, scale=args.scale,
-                  n_set0_arg=args.n_set0, f64=args.f64, want_moments=args.config == "c5" or args.moments, values=args.values)
+                  n_set0_arg=args.n_set0, f64=args.f64, want_moments=args.config == "c5" or args.moments, values=args.values, dump=dump)
+    if rank == 0 and dump is not None:
+        write_outputs(args.dump_outputs, dump)
     default_line = args.config == "c2" and not args.op and not args.tracks and not args.chroms and args.scale == 1.0 and not args.f64 and args.values == "k8"
     # multi-GPU: the e2e bulk leg per rank (every GPU has its own PCIe link) -- all ranks take part
     e2e_multi = None
-    if world > 1 and not args.no_e2e:
+    if args.full and world > 1 and not args.no_e2e:
         e2e_multi = e2e_sharded(ctx, ops[-1], N, args.mean_run, min(args.e2e_mbp, 100.0))
         trim_pools()
     if rank == 0:
-        if world == 1 and not args.no_e2e:
+        if args.full and world == 1 and not args.no_e2e:
             fit = min(1.0, 100.0 / N) * (args.scale if args.scale < 1 else 1.0)
             try:
                 res["e2e"] = e2e_dropin(ops[-1], N, args.mean_run, args.e2e_mbp * fit, device)
@@ -1149,11 +1238,11 @@ def main():
             res["value_e2e_bigwig_steady"] = res.get("e2e_bigwig", {}).get("steady_bp_per_s")
         if e2e_multi is not None:
             res["e2e_sharded"] = e2e_multi
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             with_cpu(res, chrom_ids, ops, N, args.mean_run, not args.no_many_core)
         res.pop("_chrom_lens", None)
     # the other BASELINE configurations and run lengths, as sub-records of the default line (one GPU)
-    if world == 1 and default_line and not args.no_sub:
+    if args.full and world == 1 and default_line and not args.no_sub:
         subs, runs, others = {}, {}, {}
 
         def sub(name, ops_, N_, chroms_, mean_run_, f64=False, cpu=True, moments=False, values="k8"):

@@ -53,22 +53,82 @@ def build(force=False):
         _locked_make("all")
 
 
+def _absolute_needed(path):
+    """The DT_NEEDED entries of an ELF64 little-endian shared object that name a library by absolute path, as
+    (file offset of the entry's d_val, d_val, length of the directory part including its last '/'), and the file's bytes."""
+    import struct
+    with open(path, "rb") as f:
+        data = bytearray(f.read())
+    if data[:4] != b"\x7fELF" or data[4] != 2 or data[5] != 1:
+        return [], data
+    phoff, = struct.unpack_from("<Q", data, 0x20)
+    phentsize, phnum = struct.unpack_from("<HH", data, 0x36)
+    loads, dyn = [], None
+    for i in range(phnum):
+        p_type, _, p_offset, p_vaddr, _, p_filesz, _, _ = struct.unpack_from("<IIQQQQQQ", data, phoff + i * phentsize)
+        if p_type == 1:
+            loads.append((p_vaddr, p_offset, p_filesz))
+        elif p_type == 2:
+            dyn = (p_offset, p_filesz)
+    if dyn is None:
+        return [], data
+    entries = []
+    for k in range(dyn[1] // 16):
+        tag, val = struct.unpack_from("<qQ", data, dyn[0] + 16 * k)
+        if tag == 0:
+            break
+        entries.append((dyn[0] + 16 * k + 8, tag, val))
+    strtab = [v for _, t, v in entries if t == 5]                     # DT_STRTAB (an address)
+    base = [o + strtab[0] - va for va, o, n in loads if strtab and va <= strtab[0] < va + n]
+    if not base:
+        return [], data
+    out = []
+    for pos, tag, val in entries:
+        if tag == 1:                                                  # DT_NEEDED
+            a = base[0] + val
+            name = bytes(data[a:data.index(b"\0", a)])
+            if name.startswith(b"/"):
+                out.append((pos, val, name.rindex(b"/") + 1))
+    return out, data
+
+
 def build_mixed(force=False):
     """The mixed-link libraries (reference translation units + a drop-in library); see oracle/Makefile.  Skipped when
-    both are newer than the drop-in libraries they link against."""
+    both are newer than the drop-in libraries they link against -- and were linked by the current recipe (the drop-in
+    library by file name, not by the absolute path an earlier recipe recorded)."""
     if not os.path.isdir("/root/reference/src"):
         return
     mk = os.path.join(_HERE, "Makefile")
     pairs = (("amd", os.path.join(_HERE, "..", "wiggletools_amd", "csrc", "libwiggletools_amd.so")),
              ("emu", os.path.join(_HERE, "..", "tests", "emu", "libwt_dropin_emu.so")))
-    if force or not all(_newer(os.path.join(_HERE, "_ref", "libwiggletools_mixed_%s.so" % v), [lib, mk])
-                        for v, lib in pairs if os.path.exists(lib)):
+    mixed = [os.path.join(_HERE, "_ref", "libwiggletools_mixed_%s.so" % v) for v, _ in pairs]
+    if (force or not all(_newer(m, [lib, mk]) for m, (v, lib) in zip(mixed, pairs) if os.path.exists(lib))
+            or any(os.path.exists(m) and _absolute_needed(m)[0] for m in mixed)):
         _locked_make("mixed")
 
 
 def mixed_path(variant):
+    """The mixed-link library of `variant`.  One that names its drop-in library by an absolute path (linked by an earlier
+    recipe, possibly in another checkout) is served as a copy beside it whose DT_NEEDED entries point at the file-name
+    part of the same strings: the loader then finds this checkout's drop-in library through the $ORIGIN-relative run
+    path both recipes record."""
     p = os.path.join(_HERE, "_ref", "libwiggletools_mixed_%s.so" % variant)
-    return p if os.path.exists(p) else None
+    if not os.path.exists(p):
+        return None
+    fix, data = _absolute_needed(p)
+    if not fix:
+        return p
+    import struct
+    q = os.path.join(_HERE, "_ref", "libwiggletools_mixed_%s_byname.so" % variant)
+    if not _newer(q, [p]):
+        for pos, val, cut in fix:
+            struct.pack_into("<Q", data, pos, val + cut)
+        tmp = "%s.tmp.%d" % (q, os.getpid())
+        with open(tmp, "wb") as f:
+            f.write(data)
+        os.chmod(tmp, 0o755)
+        os.replace(tmp, q)
+    return q
 
 
 _oracle = None

@@ -8,7 +8,7 @@ mkdir -p $OUT
 cd $R
 for c in c2 c3 c4 c5; do
   extra="--no-e2e"; [ $c = c2 ] && extra=""
-  timeout 900 python bench.py --config $c --steps 3 --warmup 1 $extra > $OUT/bench_$c.log 2>&1
+  timeout 900 python bench.py --full --config $c --steps 3 --warmup 1 $extra > $OUT/bench_$c.log 2>&1
   tail -1 $OUT/bench_$c.log > $OUT/bench_$c.json
   python - <<PY
 import json

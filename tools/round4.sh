@@ -84,7 +84,7 @@ json.dump(summary, open(os.path.join(out, "pmc_sq_summary.json"), "w"), indent=1
 print(json.dumps(summary, indent=1)[:3500])
 PY
 cd $R
-(time python bench.py) > $OUT/bench_default.json 2> $OUT/bench_default.err
+(time python bench.py --full) > $OUT/bench_default.json 2> $OUT/bench_default.err
 tail -3 $OUT/bench_default.err
 python - <<PY
 import json

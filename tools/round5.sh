@@ -82,7 +82,7 @@ s = json.load(open("$OUT/pmc_sq_summary.json"))
 if "traffic" in s: json.dump(s["traffic"], open("$R/profiles/traffic.json", "w"), indent=1)
 PY
 cp $R/profiles/traffic.json $OUT/traffic.json
-(time python bench.py) > $OUT/bench_default.json 2> $OUT/bench_default.err
+(time python bench.py --full) > $OUT/bench_default.json 2> $OUT/bench_default.err
 tail -3 $OUT/bench_default.err
 python - <<PY
 import json

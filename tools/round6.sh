@@ -111,7 +111,7 @@ if [ -z "$SKIP_BW" ]; then
 fi
 cd $R
 if [ -z "$SKIP_BENCH" ]; then
-  (time python bench.py --full-record $OUT/bench_default_full.json) > $OUT/bench_default.json 2> $OUT/bench_default.err
+  (time python bench.py --full --full-record $OUT/bench_default_full.json) > $OUT/bench_default.json 2> $OUT/bench_default.err
   tail -4 $OUT/bench_default.err | cut -c1-300
   tail -1 $OUT/bench_default.json | cut -c1-3000
 fi
