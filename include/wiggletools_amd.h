@@ -538,6 +538,9 @@ int64_t wtamd_pipe_bw_fill_sections(const wtamd_pipe *);
  * back to the host decoder from that batch on -- libBigWig, which the reference reads through, checks none of these
  * extents (src/bigWiggleReader.c:52-83). */
 unsigned wtamd_pipe_bw_error(const wtamd_pipe *);
+/* File-byte batches decoded a second time at collect because they held more intervals than the run lists sized from the
+ * earlier batches' density (WT_BW_ERR_CAPACITY on the first pass), since the pipe was created. */
+int64_t wtamd_pipe_bw_redone(const wtamd_pipe *);
 
 /* Pinned (page-locked, DMA-able) host memory for bulk sources. */
 void *wtamd_host_alloc(size_t bytes);

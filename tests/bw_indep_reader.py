@@ -74,22 +74,7 @@ class IndependentBigWig:
         raw = self.b[d_off:d_off + d_size]
         if self.uncompress_buf:
             raw = zlib.decompress(raw)
-        cid, c_start, c_end, step, span, typ, _r, count = struct.unpack_from("<IIIIIBBH", raw, 0)
-        body = memoryview(raw)[24:]
-        if typ == 1:        # bedGraph: start, end, value
-            a = np.frombuffer(body, dtype=np.dtype([("s", "<u4"), ("e", "<u4"), ("v", "<f4")]), count=count)
-            s, e, v = a["s"].astype(np.int64), a["e"].astype(np.int64), a["v"].copy()
-        elif typ == 2:      # variableStep: start, value; span from the header
-            a = np.frombuffer(body, dtype=np.dtype([("s", "<u4"), ("v", "<f4")]), count=count)
-            s = a["s"].astype(np.int64)
-            e, v = s + span, a["v"].copy()
-        elif typ == 3:      # fixedStep: value; start / step / span from the header
-            v = np.frombuffer(body, dtype="<f4", count=count).copy()
-            s = c_start + step * np.arange(count, dtype=np.int64)
-            e = s + span
-        else:
-            raise ValueError("unknown section type %d" % typ)
-        return cid, s, e, v
+        return parse_section(raw)
 
     def intervals(self, chrom, lo=0, hi=None):
         """(start0, end0, value) of the items overlapping [lo, hi) of `chrom`, sorted by start."""
@@ -113,6 +98,33 @@ class IndependentBigWig:
         s, e, v = np.concatenate(S), np.concatenate(E), np.concatenate(V)
         order = np.argsort(s, kind="stable")
         return s[order], e[order], v[order]
+
+
+def parse_section(raw):
+    """The plain bytes of one data section (header + items) -> (chrom id, start0, end0, value): items 0-based half-open,
+    in file order, values float32.  ValueError when the header's item count does not fit the bytes or the type is
+    unknown."""
+    if len(raw) < 24:
+        raise ValueError("section shorter than its header")
+    cid, c_start, c_end, step, span, typ, _r, count = struct.unpack_from("<IIIIIBBH", raw, 0)
+    body = memoryview(raw)[24:]
+    size = {1: 12, 2: 8, 3: 4}.get(typ)
+    if size is None:
+        raise ValueError("unknown section type %d" % typ)
+    if size * count > len(body):
+        raise ValueError("%d items of type %d do not fit %d bytes" % (count, typ, len(body)))
+    if typ == 1:        # bedGraph: start, end, value
+        a = np.frombuffer(body, dtype=np.dtype([("s", "<u4"), ("e", "<u4"), ("v", "<f4")]), count=count)
+        s, e, v = a["s"].astype(np.int64), a["e"].astype(np.int64), a["v"].copy()
+    elif typ == 2:      # variableStep: start, value; span from the header
+        a = np.frombuffer(body, dtype=np.dtype([("s", "<u4"), ("v", "<f4")]), count=count)
+        s = a["s"].astype(np.int64)
+        e, v = s + span, a["v"].copy()
+    else:               # fixedStep: value; start / step / span from the header
+        v = np.frombuffer(body, dtype="<f4", count=count).copy()
+        s = c_start + step * np.arange(count, dtype=np.int64)
+        e = s + span
+    return cid, s, e, v
 
 
 def parse_wig(path):

@@ -45,6 +45,18 @@ def build_variant(name, flags):
     return _compile(so, srcs, list(flags) + [srcs[0], "-lm"])
 
 
+def build_inflate_variant(name, flags):
+    """tests/emu/libwt_inflate_<name>.so: the lane state machine of csrc/wt_inflate.h alone (wt_inflate_variant.cpp),
+    compiled with extra flags (e.g. -DWT_INF_ROUND=3), rebuilt when a source is newer.  Exports wtemu_inflate and
+    wtemu_inflate_ring like the emulated pipeline."""
+    so = os.path.join(HERE, "libwt_inflate_%s.so" % name)
+    srcs = [os.path.join(HERE, "wt_inflate_variant.cpp"), os.path.join(HERE, "wt_inflate_emu.h"),
+            os.path.join(HERE, "..", "..", "wiggletools_amd", "csrc", "wt_inflate.h")]
+    if os.path.exists(so) and all(os.path.getmtime(so) >= os.path.getmtime(s) for s in srcs):
+        return so
+    return _compile(so, srcs, list(flags) + [srcs[0]])
+
+
 def build_dropin(force=False):
     """tests/emu/libwt_dropin_emu.so: the product's drop-in layer (csrc/wt_iter_abi.cpp,
     csrc/wt_defaults.cpp) linked against the emulated pipeline (wt_pipe_emu.cpp + wt_emu.cpp)."""
@@ -54,7 +66,7 @@ def build_dropin(force=False):
             os.path.join(csrc, "wt_iter_abi.cpp"), os.path.join(csrc, "wt_defaults.cpp"), os.path.join(csrc, "wt_bigwig.cpp")]
     deps = srcs + [os.path.join(csrc, h) for h in ("wt_core.h", "wt_plan.h", "wt_delta.h", "wt_walk.h", "wt_mwalk.h", "wt_abi_common.h", "wt_abi_feeder.h", "wt_abi_reduce.h", "wt_abi_readers.h", "wt_abi_bwdev.h", "wt_abi_ops.h", "wt_abi_integrators.h", "wt_bufreader.h", "wt_inflate.h", "wt_bwdev_core.h",
                                                     "wt_mapop.h", "wt_bigwig_int.h")] + \
-        [os.path.join(HERE, "..", "..", "include", "wiggletools_amd.h")]
+        [os.path.join(HERE, "..", "..", "include", "wiggletools_amd.h"), os.path.join(HERE, "wt_inflate_emu.h")]
     if not force and os.path.exists(so) and all(os.path.getmtime(so) >= os.path.getmtime(s) for s in deps):
         return so
     if force and os.path.exists(so):

@@ -18,6 +18,7 @@
 #include "../../wiggletools_amd/csrc/wt_mapop.h"
 #include "../../wiggletools_amd/csrc/wt_inflate.h"
 #include "../../wiggletools_amd/csrc/wt_bwdev_core.h"
+#include "wt_inflate_emu.h"
 
 extern "C" long long wtemu_reduce(int n_chrom, int n_tracks, const int64_t *seg_off, const int32_t *start,
                                   const int32_t *finish, const void *value, int value_is_f64, const double *defaults,
@@ -346,34 +347,9 @@ int wtamd_pipe_integrate_held(wtamd_pipe *p, double *integ) {
 }
 
 // ---- BigWig sections "on device": the kernels' own per-lane / per-item code (csrc/wt_inflate.h, csrc/wt_bwdev_core.h)
-// run one section after the other -- what csrc/wt_bwdev.hip runs one lane / one wavefront per section.
+// run one section after the other -- what csrc/wt_bwdev.hip runs one lane / one wavefront per section
+// (the lane's state machine: wt_inflate_emu.h).
 
-// One zlib (or raw deflate) stream through the lane state machine; returns bytes produced or -(error).
-}  // extern "C"
-template <int RING>
-static long long emu_inflate_ring(const uint8_t *src, long long n, uint8_t *dst, long long cap, int raw_deflate, long long *steps, uint32_t *end_byte = nullptr) {
-    std::vector<uint8_t> perm(WT_INF_PERM + 8, 0);
-    std::vector<uint32_t> ring(RING, 0);
-    WtInfMem m{perm.data(), ring.data(), 1};
-    // the decoder reads whole aligned 16-byte chunks around the stream and writes whole words: private padded copies
-    std::vector<uint8_t> in((size_t) n + 96, 0), out(((size_t) cap + 3) / 4 * 4 + 8, 0);
-    const int mis = (int) (n % 16);             // any alignment must work
-    if (n > 0) memcpy(in.data() + 32 + mis, src, (size_t) n);
-    WtInflateT<RING> z;
-    wt_inf_begin(z, in.data() + 32 + mis, (uint32_t) n, out.data(), (uint32_t) cap, raw_deflate != 0);
-    long long rounds = 0;
-    while (wt_inf_land(z, m)) {
-        for (int r = 0; r < WT_INF_ROUND; r++) wt_inf_step(z, m);
-        rounds++;
-    }
-    if (steps) *steps = rounds * WT_INF_ROUND;
-    const long long r = (long long) wt_inf_finish(z);
-    if (end_byte) *end_byte = wt_inf_end_byte(z);
-    if (r > 0) memcpy(dst, out.data(), (size_t) r);
-    return r;
-}
-
-extern "C" {
 // One zlib (or raw deflate) stream through the lane state machine; returns bytes produced or -(error).
 long long wtemu_inflate(const uint8_t *src, long long n, uint8_t *dst, long long cap, int raw_deflate) {
     return emu_inflate_ring<WT_INF_RING>(src, n, dst, cap, raw_deflate, nullptr);
@@ -452,6 +428,9 @@ unsigned wtemu_bw_decode(const uint8_t *bytes, const wtamd_bw_section *secs, lon
 int64_t wtamd_pipe_bw_fill_sections(const wtamd_pipe *p) { return p ? 4096 : 0; }
 
 unsigned wtamd_pipe_bw_error(const wtamd_pipe *p) { return p ? p->last_bw_err : 0u; }
+
+// (run lists are sized by the host's bound here: a batch is never decoded twice)
+int64_t wtamd_pipe_bw_redone(const wtamd_pipe *) { return 0; }
 
 int wtamd_pipe_bw_reserve(wtamd_pipe *p, int64_t n_bytes, int64_t n_sections, uint8_t **bytes, wtamd_bw_section **sections) {
     if (!p || p->acquired < 0 || n_bytes < 0 || n_sections < 0 || !bytes || !sections) { g_err = "wtamd_pipe_bw_reserve: bad arguments"; return WTAMD_ERR_ARG; }

@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 from bw_writer import write_bigwig
-from test_bwreader import G, WI, _bind, _blocks, _expected, _pops, _reduce, _same, _write_set
+from test_bwreader import G, WI, _bind, _blocks, _expected, _no_fallback, _pops, _reduce, _same, _write_set
 from wiggletools_amd import bigwig
 from wiggletools_amd.pipe import PipeStats
 
@@ -253,13 +253,15 @@ def test_corrupt_section_fails_loudly_emu(tmp_path):
 
 
 @pytest.mark.gpu
-def test_device_decode_equals_host_decoder_gpu(amd_lib, oracle, tmp_path, monkeypatch):
+def test_device_decode_equals_host_decoder_gpu(amd_lib, oracle, tmp_path, monkeypatch, capfd):
     _device_vs_host(amd_lib, oracle, tmp_path, monkeypatch)
+    _no_fallback(capfd)
 
 
 @pytest.mark.gpu
-def test_device_decode_seek_gpu(amd_lib, oracle, tmp_path, monkeypatch):
+def test_device_decode_seek_gpu(amd_lib, oracle, tmp_path, monkeypatch, capfd):
     _seek_cases(amd_lib, oracle, tmp_path, monkeypatch)
+    _no_fallback(capfd)
 
 
 def _one_track(t, L):
@@ -275,7 +277,7 @@ def _one_track(t, L):
 
 
 @pytest.mark.gpu
-def test_device_decode_larger_files_gpu(amd_lib, oracle, tmp_path, monkeypatch):
+def test_device_decode_larger_files_gpu(amd_lib, oracle, tmp_path, monkeypatch, capfd):
     """Bench-style files (wiggletools_amd/bwwrite.py: 1024-item bedGraph sections, zlib level 1), 12 tracks x 3 Mbp:
     thousands of sections per batch through the lane-per-section inflate; == host decoder run for run."""
     from wiggletools_amd import bwwrite
@@ -295,6 +297,7 @@ def test_device_decode_larger_files_gpu(amd_lib, oracle, tmp_path, monkeypatch):
         assert (st.bw_sections > 0) == (dev == "1")
     assert len(res["1"]) > 1_000_000
     assert res["1"] == res["0"]
+    _no_fallback(capfd)
 
 
 def _genome_fileset(tmp_path, n_tracks, chroms, seed, items=64):
@@ -355,8 +358,9 @@ def test_device_decode_multichrom_emu(emu_lib, oracle, tmp_path, monkeypatch):
 
 
 @pytest.mark.gpu
-def test_device_decode_multichrom_gpu(amd_lib, oracle, tmp_path, monkeypatch):
+def test_device_decode_multichrom_gpu(amd_lib, oracle, tmp_path, monkeypatch, capfd):
     _multichrom(amd_lib, oracle, tmp_path, monkeypatch, n_tracks=12, scale=20000, batch_sections=1200, min_span=30000)
+    _no_fallback(capfd)
 
 
 def _shrink_leaf(path, leaf_no, by):

@@ -187,14 +187,22 @@ def test_bigwig_small_batches_emu(emu_lib, oracle, tmp_path, monkeypatch):
     _same(_blocks(emu_lib, wi), _expected(oracle, paths, "mean"))
 
 
+def _no_fallback(capfd):
+    """The device decoded every file-byte batch: no note that the drop-in layer went back to the host decoder."""
+    err = capfd.readouterr().err
+    assert "rejected a batch" not in err and "continuing with the host decoder" not in err, err[-2000:]
+
+
 @pytest.mark.gpu
-def test_bigwig_reader_pop_and_seek_gpu(amd_lib, tmp_path):
+def test_bigwig_reader_pop_and_seek_gpu(amd_lib, tmp_path, capfd):
     _run_single_reader(amd_lib, tmp_path)
+    _no_fallback(capfd)
 
 
 @pytest.mark.gpu
-def test_bigwig_files_to_reducers_gpu(amd_lib, oracle, tmp_path):
+def test_bigwig_files_to_reducers_gpu(amd_lib, oracle, tmp_path, capfd):
     _run_all(amd_lib, oracle, tmp_path)
+    _no_fallback(capfd)
 
 
 def _close_case(L, tmp_path):
@@ -224,8 +232,9 @@ def test_bigwig_reader_close_emu(emu_lib, tmp_path):
 
 
 @pytest.mark.gpu
-def test_bigwig_reader_close_gpu(amd_lib, tmp_path):
+def test_bigwig_reader_close_gpu(amd_lib, tmp_path, capfd):
     _close_case(amd_lib, tmp_path)
+    _no_fallback(capfd)
 
 
 def test_array_writer_round_trip(tmp_path):

@@ -859,6 +859,8 @@ static int64_t wt_align256(int64_t x) { return (x + 255) & ~(int64_t) 255; }
 
 unsigned wtamd_pipe_bw_error(const wtamd_pipe *p) { return p ? p->last_bw_err : 0u; }
 
+int64_t wtamd_pipe_bw_redone(const wtamd_pipe *p) { return p ? p->bw_redone : 0; }
+
 int64_t wtamd_pipe_bw_fill_sections(const wtamd_pipe *p) {
     if (!p || p->slots.empty() || !p->slots[0].ts) return 0;
     return (int64_t) wt_bw_fill_sections(p->slots[0].ts->num_cu);

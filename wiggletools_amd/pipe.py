@@ -41,6 +41,17 @@ class PipeStats(C.Structure):
                 ("bw_sections", C.c_int64), ("bw_decode_ms", C.c_double)]
 
 
+class BwSection(C.Structure):      # wtamd_bw_section
+    _fields_ = [("comp_off", C.c_int64), ("comp_size", C.c_uint32), ("track", C.c_int32),
+                ("leaf_start", C.c_uint32), ("leaf_end", C.c_uint32)]
+
+
+class BwTrack(C.Structure):        # wtamd_bw_track
+    _fields_ = [("chrom_id", C.c_uint32), ("chrom_len", C.c_uint32), ("box", C.c_int32), ("compressed", C.c_int32),
+                ("clip_lo", C.c_int32), ("clip_hi", C.c_int32), ("first_section", C.c_int32), ("n_sections", C.c_int32),
+                ("plain_bytes", C.c_uint32), ("reserved", C.c_int32)]
+
+
 def _view(ptr, n, dtype):
     if not ptr or n <= 0:
         return np.zeros(0, dtype)
@@ -64,6 +75,24 @@ def _bind(L):
     L.wtamd_pipe_get_stats.argtypes = [C.c_void_p, C.POINTER(PipeStats)]
     L.wtamd_last_error.restype = C.c_char_p
     L._wt_pipe_bound = True
+    return L
+
+
+def _bind_bw(L):
+    """The file-byte door (wtamd_pipe_bw_*), bound on first use: a pipe that only ever takes run lists needs none of
+    its symbols."""
+    if getattr(L, "_wt_pipe_bw_bound", False):
+        return L
+    L.wtamd_pipe_bw_reserve.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.POINTER(C.c_uint8)),
+                                        C.POINTER(C.POINTER(BwSection))]
+    L.wtamd_pipe_submit_bw.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(BwTrack), C.c_int32, C.c_int32]
+    L.wtamd_pipe_bw_error.argtypes = [C.c_void_p]
+    L.wtamd_pipe_bw_error.restype = C.c_uint
+    L.wtamd_pipe_bw_fill_sections.argtypes = [C.c_void_p]
+    L.wtamd_pipe_bw_fill_sections.restype = C.c_int64
+    L.wtamd_pipe_bw_redone.argtypes = [C.c_void_p]
+    L.wtamd_pipe_bw_redone.restype = C.c_int64
+    L._wt_pipe_bw_bound = True
     return L
 
 
@@ -117,6 +146,34 @@ class Pipe:
     def submit(self, lo, hi, f64=False):
         self._check(self.L.wtamd_pipe_submit(self._h, int(f64), int(lo), int(hi)))
         self._b = None
+
+    # ---- BigWig file bytes decoded on the device (wtamd_pipe_bw_reserve / wtamd_pipe_submit_bw) ----
+    def bw_reserve(self, n_bytes, n_sections):
+        """(bytes, sections) of the acquired slot: a uint8 numpy view of `n_bytes` and a BwSection array of `n_sections`,
+        both valid until submit_bw / cancel."""
+        pb, ps = C.POINTER(C.c_uint8)(), C.POINTER(BwSection)()
+        self._check(_bind_bw(self.L).wtamd_pipe_bw_reserve(self._h, int(n_bytes), int(n_sections), C.byref(pb), C.byref(ps)))
+        data = np.ctypeslib.as_array(pb, shape=(int(n_bytes),)) if n_bytes > 0 else np.zeros(0, np.uint8)
+        return data, C.cast(ps, C.POINTER(BwSection * int(n_sections))).contents if n_sections > 0 else (BwSection * 0)()
+
+    def submit_bw(self, n_bytes, n_sections, tracks, lo, hi):
+        """Ships the acquired slot as file bytes; `tracks`: n_tracks BwTrack (a ctypes array or a list)."""
+        if not isinstance(tracks, C.Array):
+            tracks = (BwTrack * len(tracks))(*tracks)
+        assert len(tracks) == self.n_tracks
+        self._check(_bind_bw(self.L).wtamd_pipe_submit_bw(self._h, int(n_bytes), int(n_sections), tracks, int(lo), int(hi)))
+        self._b = None
+
+    def bw_error(self):
+        """Error bits of the last failed collect of a file-byte batch (0: it did not fail there)."""
+        return _bind_bw(self.L).wtamd_pipe_bw_error(self._h)
+
+    def bw_fill_sections(self):
+        return _bind_bw(self.L).wtamd_pipe_bw_fill_sections(self._h)
+
+    def bw_redone(self):
+        """File-byte batches decoded a second time because their run lists were sized too small."""
+        return _bind_bw(self.L).wtamd_pipe_bw_redone(self._h)
 
     def cancel(self):
         self._check(self.L.wtamd_pipe_cancel(self._h))
