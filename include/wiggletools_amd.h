@@ -321,6 +321,26 @@ int wtamd_pearson_moments(wtamd_trackset *ts, double *moments6);
 void wtamd_pearson_merge(double *a6, const double *b6);     /* a := a (+) b, b after a in genome order; HOST */
 double wtamd_pearson_finish(const double *m6);               /* T_XY / sqrt(T_XX T_YY), NaN if 0 (statistics.c:421-423) */
 
+/* The reference's other genome-wide statistics over a device run list -- varI / stddevI / CVI, maxI / minI and the
+ * span (statistics.c:129-326) -- from ONE pass:
+ *     moments6 = { sum of L v, span = sum of L, T = sum of L (v - sum / span)^2, min, max, 0 },  L = finish - start,
+ * over the runs whose value is not NaN (min and max are NaN when there is none).  T is the reference's
+ * VarianceData.T (:232-252): it updates T run by run, here lanes' partial {span, sum, T} are merged pairwise in a
+ * fixed order, so T and sum agree to rounding (the same run list always gives the same bits); span is exact,
+ * min / max bit for bit (the earlier run wins between -0.0 and 0.0, as in the reference). */
+int wtamd_runs_moments(const wtamd_runs *runs, int64_t n_runs, double *moments6, void *stream);
+/* a := a (+) b, b after a in genome order (chromosomes on different GPUs, batches of a pipeline); HOST */
+void wtamd_moments_merge(double *a6, const double *b6);
+/* The reference's closing arithmetic in its own order (statistics.c:259,288-289,312-314): whatever that gives for
+ * an empty or one-base-pair input (-0.0, NaN, inf) is what comes back; HOST */
+#define WTAMD_STAT_VAR 0    /* T / (span - 1) */
+#define WTAMD_STAT_STDDEV 1 /* sqrt of that */
+#define WTAMD_STAT_CV 2     /* that / (sum / span) */
+#define WTAMD_STAT_MAX 3
+#define WTAMD_STAT_MIN 4
+#define WTAMD_STAT_SPAN 5
+double wtamd_moments_finish(const double *m6, int kind);
+
 /* The reference's `map`-able unary operators (src/unaryOps.c: scale :650-664, offset :722-734,
  * ln / log :760-813, exp :823-866, pow :873-899, abs :934-949; commandParser.c:115-211) applied to
  * whole run lists on device before they are multiplexed. */
@@ -481,6 +501,11 @@ int wtamd_pipe_set_compress(wtamd_pipe *, int on);
  * per run.  Sums are two-level (per lane slice, then ordered merge): agreement with the reference's sequential
  * accumulation to rounding.  Not together with WTAMD_PIPE_COMPRESS. */
 int wtamd_pipe_set_integrate(wtamd_pipe *, int on);
+/* on == 2 (reducers only): the batch's six run moments of wtamd_runs_moments come home in integ[0..5] instead, for
+ * varI / stddevI / CVI / maxI / minI / span; merge batches in order with wtamd_moments_merge.  on == 1 is unchanged
+ * (integ[2..5] zero for a reducer).  wtamd_pipe_integrate_modes: the highest `on` this pipe serves (2 for a reducer,
+ * 1 for the Multiplexer tile) -- a pipeline that predates mode 2 does not export it. */
+int wtamd_pipe_integrate_modes(const wtamd_pipe *);
 /* The same integrals of the batch currently held (collected, not released) when it travelled the ordinary way
  * -- the batch a reducer's constructor primed with before an integrator took it over.  integ[6] as above. */
 int wtamd_pipe_integrate_held(wtamd_pipe *, double *integ);
@@ -594,6 +619,17 @@ int wtamd_BigWiggleReader_close(WiggleIterator *wi);
 WiggleIterator *wtamd_AUCIntegrator(WiggleIterator *wi);
 WiggleIterator *wtamd_MeanIntegrator(WiggleIterator *wi);
 WiggleIterator *wtamd_PearsonIntegrator(Multiplexer *multi);
+/* varI / stddevI / CVI / maxI / minI (statistics.c:159-326, commandParser.c:653-704) and the SpanIntegrator the
+ * reference's library exports (:129-157), under the same contract: fused over a reducer of this library (six doubles
+ * per batch come home, wtamd_pipe_set_integrate mode 2), the reference's per-run pass-through otherwise.  One departure:
+ * the reference's VarianceCorePop returns on a NaN run WITHOUT popping its source (:238-239), so its varI / stddevI / CVI
+ * never end over a source with a NaN run; these skip NaN runs, as its min / max / span / mean / AUC do. */
+WiggleIterator *wtamd_VarianceIntegrator(WiggleIterator *wi);
+WiggleIterator *wtamd_StandardDeviationIntegrator(WiggleIterator *wi);
+WiggleIterator *wtamd_CoefficientOfVariationIntegrator(WiggleIterator *wi);
+WiggleIterator *wtamd_MaxIntegrator(WiggleIterator *wi);
+WiggleIterator *wtamd_MinIntegrator(WiggleIterator *wi);
+WiggleIterator *wtamd_SpanIntegrator(WiggleIterator *wi);
 /* Consumer door, for reducers built by this library: the runs from the iterator's current element
  * to the end of the batch it belongs to, as arrays valid until the next call on `wi`.  Returns the
  * number of runs (0 and wi->done at the end).  Mixes freely with pop(). */

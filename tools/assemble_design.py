@@ -99,6 +99,8 @@ add("### 4.8 Integrators, run compression, the `map`-able operators")
 add("")
 add(body(7, "#### `wt_auc_kernel`, `wt_pearson_kernel`, `wt_extents_kernel`, `wt_compress_*`"))
 add("")
+add(new("048_moments"))
+add("")
 add(body(8, "#### `wm_map_kernel` / `wm_compact_kernel` — the `map`-able unary operators (`csrc/wt_map.hip`)"))
 add("")
 add(body(13, "#### Operator chains inside the pipeline (`wt_map_chain_async`, `wtamd_pipe_set_map`)"))
@@ -142,6 +144,8 @@ add("")
 add(new("068_measured"))
 add("")
 add(body(36, "## 7. Fused integrators through the reference API"))
+add("")
+add(new("071_moment_integrators"))
 add("")
 add(body(16, "## 8. Multi-GPU"))
 add("")

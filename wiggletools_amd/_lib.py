@@ -82,6 +82,11 @@ def lib():
     L.wtamd_pearson_merge.restype = None
     L.wtamd_pearson_finish.argtypes = [C.c_void_p]
     L.wtamd_pearson_finish.restype = C.c_double
+    L.wtamd_runs_moments.argtypes = [C.POINTER(Runs), C.c_int64, C.c_void_p, C.c_void_p]
+    L.wtamd_moments_merge.argtypes = [C.c_void_p, C.c_void_p]
+    L.wtamd_moments_merge.restype = None
+    L.wtamd_moments_finish.argtypes = [C.c_void_p, C.c_int]
+    L.wtamd_moments_finish.restype = C.c_double
     L.wtamd_get_stats.argtypes = [C.c_void_p, C.POINTER(Stats)]
     L.wtamd_bw_open.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
     L.wtamd_bw_close.argtypes = [C.c_void_p]

@@ -134,4 +134,33 @@ double wtamd_pearson_finish(const double *m) {
     return den ? m[4] / sqrt(den) : __builtin_nan("");
 }
 
+// Run moments {sum, span, T, min, max, spare} (wtamd_runs_moments, wtamd_pipe_set_integrate mode 2): a := a (+) b, b after a
+// in genome order -- the pairwise form of the reference's VarianceCorePop step (statistics.c:241-249); the earlier of two
+// extremes that compare equal stays (:176,206: strict > / <).
+void wtamd_moments_merge(double *a, const double *b) {
+    if (b[1] == 0) return;
+    if (a[1] == 0) { memcpy(a, b, sizeof(double) * 6); return; }
+    const double n = a[1] + b[1];
+    const double dm = b[0] / b[1] - a[0] / a[1];
+    a[2] += b[2] + dm * dm * (a[1] * b[1] / n);
+    a[0] += b[0];
+    a[1] = n;
+    if (a[3] != a[3] || b[3] < a[3]) a[3] = b[3];
+    if (a[4] != a[4] || b[4] > a[4]) a[4] = b[4];
+}
+
+// statistics.c:259 (var), :288-289 (stddev), :312-314 (CV) in the reference's order (its count is a long: count - 1 is exact
+// here too, a span is an integer below 2^53); max / min / span as they are.
+double wtamd_moments_finish(const double *m, int kind) {
+    if (kind == WTAMD_STAT_MAX) return m[4];
+    if (kind == WTAMD_STAT_MIN) return m[3];
+    if (kind == WTAMD_STAT_SPAN) return m[1];
+    double res = m[2] / (m[1] - 1);
+    if (kind == WTAMD_STAT_VAR) return res;
+    res = sqrt(res);
+    if (kind == WTAMD_STAT_STDDEV) return res;
+    if (kind == WTAMD_STAT_CV) return res / (m[0] / m[1]);
+    return __builtin_nan("");
+}
+
 }  // extern "C"

@@ -550,6 +550,12 @@ int wtamd_BigWiggleReader_close(WiggleIterator *wi) {
 
 WiggleIterator *wtamd_AUCIntegrator(WiggleIterator *wi) { return make_integrator(wi, nullptr, 0); }
 WiggleIterator *wtamd_MeanIntegrator(WiggleIterator *wi) { return make_integrator(wi, nullptr, 1); }
+WiggleIterator *wtamd_VarianceIntegrator(WiggleIterator *wi) { return make_integrator(wi, nullptr, 3 + WTAMD_STAT_VAR); }
+WiggleIterator *wtamd_StandardDeviationIntegrator(WiggleIterator *wi) { return make_integrator(wi, nullptr, 3 + WTAMD_STAT_STDDEV); }
+WiggleIterator *wtamd_CoefficientOfVariationIntegrator(WiggleIterator *wi) { return make_integrator(wi, nullptr, 3 + WTAMD_STAT_CV); }
+WiggleIterator *wtamd_MaxIntegrator(WiggleIterator *wi) { return make_integrator(wi, nullptr, 3 + WTAMD_STAT_MAX); }
+WiggleIterator *wtamd_MinIntegrator(WiggleIterator *wi) { return make_integrator(wi, nullptr, 3 + WTAMD_STAT_MIN); }
+WiggleIterator *wtamd_SpanIntegrator(WiggleIterator *wi) { return make_integrator(wi, nullptr, 3 + WTAMD_STAT_SPAN); }
 WiggleIterator *wtamd_PearsonIntegrator(Multiplexer *multi) {
     if (multi->count != 2) { puts("wtamd_PearsonIntegrator: the Multiplexer must hold exactly two tracks"); exit(1); }
     return make_integrator(nullptr, multi, 2);

@@ -36,6 +36,9 @@ int wt_bw_decode_async(const void *h_bytes, void *d_bytes, long long n_bytes, co
                        float *o_value, int64_t *d_seg_off, unsigned long long *h_status, int copy_blocks, hipStream_t s_copy,
                        hipEvent_t e_copied, hipStream_t s_dec);
 long long wt_compress_scratch_words(long long capacity);
+size_t wt_moments_partial_bytes(int blocks);            // wt_moments.hip
+int wt_moments_async(const int32_t *start, const int32_t *finish, const double *value, long long cap, const unsigned long long *n_dev,
+                     int blocks, void *d_partial, double *d_out6, hipStream_t st);
 int wt_compress_async(const int32_t *start, const int32_t *finish, const double *value, const unsigned long long *d_n,
                       long long capacity, unsigned long long *scratch, int32_t *o_start, int32_t *o_finish, double *o_value,
                       unsigned long long *d_n_out, hipStream_t s);
@@ -472,6 +475,7 @@ struct WtSlot {
     char *d_integ = nullptr;
     double *h_integ = nullptr;
     bool integrated = false;
+    int integ_mode = 0;             // what s.h_integ holds: 1 {sum, span} / the Pearson moments, 2 the run moments (wt_moments.hip)
 };
 
 // HIP's current device is per thread; a pipe lives on the device that was current when it was created, and the drop-in
@@ -504,7 +508,7 @@ struct wtamd_pipe {
     bool delta_failed = false;      // a batch had many inexact windows: Sum / Mean stay on the general kernel
     bool tile = false;
     bool compress = false;          // WTAMD_PIPE_COMPRESS: batches submitted from now on are merged on device before they travel
-    bool integrate = false;         // wtamd_pipe_set_integrate: batches submitted from now on are integrated on device, no runs travel
+    int integrate = 0;              // wtamd_pipe_set_integrate (0 off, 1 sums / Pearson, 2 run moments): batches submitted from now on are integrated on device, no runs travel
     bool gather = true;             // WTAMD_PIPE_GATHER=0: hipMemcpyAsync per range instead of the gather kernel
     int gather_blocks = 64;         // WTAMD_GATHER_BLOCKS
     // buffers a slot outgrew: released when the pipe is destroyed -- hipFree / hipHostFree wait for the
@@ -630,14 +634,24 @@ static int wt_pipe_enqueue_export(wtamd_pipe *p, WtSlot &s, hipEvent_t after) {
 // Integrals of the slot's (uncompressed) device runs -> s.h_integ, on `st`: {sum len * value, span} over the non-NaN
 // runs (statistics.c:62-120), or the Pearson moments of the 2-track tile (:414-465).  The run count is read on
 // the device.
+// mode 2: all six run moments {sum, span, T, min, max, 0} of wt_moments.hip (varI / stddevI / CVI / maxI / minI / span).
 #define WT_INTEG_BLOCKS 256
-static int wt_pipe_enqueue_integ(wtamd_pipe *p, WtSlot &s, hipStream_t st) {
-    const size_t need = sizeof(WtMoments) * WT_INTEG_BLOCKS + sizeof(double) * 16;
+#define WT_INTEG_PARTIAL 64         // bytes per block: WtMoments (48) or a partial of the moments kernel (64)
+static int wt_pipe_enqueue_integ(wtamd_pipe *p, WtSlot &s, hipStream_t st, int mode) {
+    static_assert(sizeof(WtMoments) <= WT_INTEG_PARTIAL, "partials of the integrators");
+    const size_t need = (size_t) WT_INTEG_PARTIAL * WT_INTEG_BLOCKS + sizeof(double) * 16;
+    if (wt_moments_partial_bytes(WT_INTEG_BLOCKS) > (size_t) WT_INTEG_PARTIAL * WT_INTEG_BLOCKS) return wt_fail(WTAMD_ERR_INTERNAL, "partials of the moments kernel");
     if (!s.d_integ) WT_HIP(wt_dev_alloc((void **) &s.d_integ, need));
     if (!s.h_integ) { WT_HIP(wt_host_alloc((void **) &s.h_integ, sizeof(double) * 8)); }
     const unsigned long long *n_dev = s.ts->d_counters + WT_CTR_RUNS;
-    double *d_out = (double *) (s.d_integ + sizeof(WtMoments) * WT_INTEG_BLOCKS);
-    if (p->tile) {
+    double *d_out = (double *) (s.d_integ + (size_t) WT_INTEG_PARTIAL * WT_INTEG_BLOCKS);
+    s.integ_mode = mode;
+    if (mode == 2) {
+        if (p->tile) return wt_fail(WTAMD_ERR_ARG, "the run moments are those of a reducer's output, not of a Multiplexer tile");
+        const int rc = wt_moments_async(s.d_os, s.d_of, s.d_ov, (long long) s.ocap, n_dev, WT_INTEG_BLOCKS, s.d_integ, d_out, st);
+        if (rc != WTAMD_OK) return rc;
+        WT_HIP(hipMemcpyAsync(s.h_integ, d_out, sizeof(double) * 6, hipMemcpyDeviceToHost, st));
+    } else if (p->tile) {
         if (p->cfg.n_tracks != 2) return wt_fail(WTAMD_ERR_ARG, "the fused Pearson integrator needs a Multiplexer of exactly two tracks");
         hipLaunchKernelGGL(wt_pearson_kernel, dim3(WT_INTEG_BLOCKS), dim3(256), 0, st, s.d_os, s.d_of, s.d_tile, s.d_ip, p->defaults[0],
                            p->defaults[1], (long long) s.ocap, (WtMoments *) s.d_integ, n_dev);
@@ -675,7 +689,7 @@ static int wt_pipe_finish(wtamd_pipe *p, WtSlot &s) {
             if (rc != WTAMD_OK) return wt_fail(rc, "run compression launch failed");
         }
         if (s.integrated) {
-            rc = wt_pipe_enqueue_integ(p, s, p->s_comp);
+            rc = wt_pipe_enqueue_integ(p, s, p->s_comp, s.integ_mode);
             if (rc != WTAMD_OK) return rc;
             WT_HIP(hipEventRecord(s.e_patch, p->s_comp));
             rc = wt_wait_event(s.e_patch, "patched integrals");
@@ -1215,7 +1229,7 @@ static int wt_pipe_submit_impl(wtamd_pipe *p, int value_is_f64, int32_t range_lo
     rc = wt_reduce_plan(ts, plan, op, p->cfg.desc.flags, p->cfg.desc.n_set0, &runs, p->tile ? s.d_tile : nullptr,
                         p->tile ? s.d_ip : nullptr, nullptr, p->s_comp);
     if (rc != WTAMD_OK) return rc;
-    s.integrated = p->integrate;
+    s.integrated = p->integrate != 0;
     s.compressed = p->compress && !s.integrated;
     if (s.compressed) {
         if (!s.d_cs) {          // (grow-only, with the output buffers)
@@ -1237,7 +1251,7 @@ static int wt_pipe_submit_impl(wtamd_pipe *p, int value_is_f64, int32_t range_lo
     s.export_pending = bw && sdma_out && !p->tile && !s.integrated;
     if (s.integrated) {
         // fused integrator: two (six) doubles and the counters go home, the runs stay
-        rc = wt_pipe_enqueue_integ(p, s, p->s_comp);
+        rc = wt_pipe_enqueue_integ(p, s, p->s_comp, p->integrate);
         if (rc != WTAMD_OK) return rc;
         WT_HIP(hipMemcpyAsync(ts->h_counters, ts->d_counters, sizeof(unsigned long long) * WT_CTR_N, hipMemcpyDeviceToHost, p->s_comp));
         WT_HIP(hipEventRecord(s.e_cnt, p->s_comp));
@@ -1354,7 +1368,7 @@ int wtamd_pipe_collect(wtamd_pipe *p, wtamd_pipe_result *out) {
     out->integ_valid = s.integrated ? 1 : 0;
     out->reserved = 0;
     for (int k = 0; k < 6; k++) out->integ[k] = s.integrated ? s.h_integ[k] : 0.0;
-    if (s.integrated && !p->tile) { out->integ[2] = out->integ[3] = out->integ[4] = out->integ[5] = 0.0; }
+    if (s.integrated && !p->tile && s.integ_mode != 2) { out->integ[2] = out->integ[3] = out->integ[4] = out->integ[5] = 0.0; }
     out->start = s.integrated ? nullptr : s.h_os; out->finish = s.integrated ? nullptr : s.h_of; out->value = s.integrated ? nullptr : s.h_ov;
     out->tile = (p->tile && !s.integrated) ? s.h_tile : nullptr;
     out->inplay = (p->tile && !s.integrated) ? s.h_ip : nullptr;
@@ -1383,8 +1397,14 @@ int wtamd_pipe_set_compress(wtamd_pipe *p, int on) {
 int wtamd_pipe_set_integrate(wtamd_pipe *p, int on) {
     if (!p) return wt_fail(WTAMD_ERR_ARG, "NULL argument");
     if (on && p->tile && p->cfg.n_tracks != 2) return wt_fail(WTAMD_ERR_ARG, "the fused Pearson integrator needs a Multiplexer of exactly two tracks");
-    p->integrate = on != 0;
+    if (on == 2 && p->tile) return wt_fail(WTAMD_ERR_ARG, "wtamd_pipe_set_integrate: mode 2 (run moments) needs a reducer, not a Multiplexer tile");
+    p->integrate = on == 2 ? 2 : on != 0;
     return WTAMD_OK;
+}
+
+int wtamd_pipe_integrate_modes(const wtamd_pipe *p) {
+    if (!p) return 0;
+    return p->tile ? 1 : 2;
 }
 
 int wtamd_pipe_integrate_held(wtamd_pipe *p, double *integ) {
@@ -1393,15 +1413,16 @@ int wtamd_pipe_integrate_held(wtamd_pipe *p, double *integ) {
     if (!p->held) return wt_fail(WTAMD_ERR_ARG, "wtamd_pipe_integrate_held: no collected batch");
     WtSlot &s = p->slots[(size_t) p->tail];
     for (int k = 0; k < 6; k++) integ[k] = 0.0;
-    if (!s.integrated) {
+    const int mode = p->integrate == 2 ? 2 : 1;
+    if (!s.integrated || s.integ_mode != mode) {
         // the device still holds the batch's runs (d_os / d_of / d_ov, the tile): integrate them there, now
-        int rc = wt_pipe_enqueue_integ(p, s, p->s_comp);
+        int rc = wt_pipe_enqueue_integ(p, s, p->s_comp, mode);
         if (rc != WTAMD_OK) return rc;
         WT_HIP(hipEventRecord(s.e_patch, p->s_comp));
         rc = wt_wait_event(s.e_patch, "integrals of the held batch");
         if (rc != WTAMD_OK) return rc;
     }
-    for (int k = 0; k < (p->tile ? 6 : 2); k++) integ[k] = s.h_integ[k];
+    for (int k = 0; k < (p->tile || mode == 2 ? 6 : 2); k++) integ[k] = s.h_integ[k];
     return WTAMD_OK;
 }
 

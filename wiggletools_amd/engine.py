@@ -14,6 +14,7 @@ from .runlists import RunLists
 OPS = {"sum": 0, "product": 1, "mult": 1, "mean": 2, "var": 3, "stddev": 4, "entropy": 5, "cv": 6, "CV": 6,
        "min": 7, "max": 8, "median": 9, "ttest": 10, "mwu": 11, "wilcoxon": 11}
 STRICT_SET0, STRICT_SET1 = 1, 2
+STATS = {"var": 0, "stddev": 1, "cv": 2, "CV": 2, "max": 3, "min": 4, "span": 5}      # WTAMD_STAT_*
 
 
 def opcode(op):
@@ -227,6 +228,40 @@ class DeviceRuns:
         out = C.c_double()
         _lib.check(_lib.lib().wtamd_runs_mean(C.byref(r), int(self.n if n is None else n), C.byref(out), stream))
         return out.value
+
+    def moments(self, n=None, stream=None):
+        """{sum L v, span, T = sum L (v - mean)^2, min, max, 0} over the non-NaN runs, one pass on the device
+        (wtamd_runs_moments): everything varI / stddevI / CVI / maxI / minI need; shards merge theirs in genome order with
+        shard.merge_run_moments."""
+        r = self.as_struct()
+        m = np.zeros(6, np.float64)
+        _lib.check(_lib.lib().wtamd_runs_moments(C.byref(r), int(self.n if n is None else n), m.ctypes.data, stream))
+        return m
+
+    def _stat(self, kind, n, stream):
+        m = self.moments(n, stream)
+        return _lib.lib().wtamd_moments_finish(m.ctypes.data, STATS[kind])
+
+    def var(self, n=None, stream=None):
+        """varI of the run list (reference VarianceIntegrator): T / (span - 1)."""
+        return self._stat("var", n, stream)
+
+    def stddev(self, n=None, stream=None):
+        return self._stat("stddev", n, stream)
+
+    def cv(self, n=None, stream=None):
+        return self._stat("cv", n, stream)
+
+    def max(self, n=None, stream=None):
+        """maxI (reference MaxIntegrator): NaN for a list without a non-NaN run."""
+        return self._stat("max", n, stream)
+
+    def min(self, n=None, stream=None):
+        return self._stat("min", n, stream)
+
+    def span(self, n=None, stream=None):
+        """Base pairs under the non-NaN runs (reference SpanIntegrator)."""
+        return self._stat("span", n, stream)
 
     def compress(self, out=None, n=None, stream=None):
         """Merged run list (reference CompressionWiggleIterator) as a new DeviceRuns."""

@@ -107,6 +107,44 @@ def pearson_from_moments(rows):
     return float(m[4] / np.sqrt(den)) if den else float("nan")
 
 
+def merge_run_moments(a, b):
+    """a (+) b for two run-moment vectors {sum, span, T, min, max, spare} (engine.DeviceRuns.moments, wtamd_moments_merge),
+    b after a in genome order: the pairwise form of the reference's variance update (statistics.c:241-249); of two
+    extremes that compare equal the earlier stays (:176,206)."""
+    a = np.array(a, np.float64)
+    b = np.asarray(b, np.float64)
+    if b[1] == 0:
+        return a
+    if a[1] == 0:
+        return b.copy()
+    n = a[1] + b[1]
+    dm = b[0] / b[1] - a[0] / a[1]
+    mn = b[3] if (np.isnan(a[3]) or b[3] < a[3]) else a[3]
+    mx = b[4] if (np.isnan(a[4]) or b[4] > a[4]) else a[4]
+    return np.array([a[0] + b[0], n, a[2] + (b[2] + dm * dm * (a[1] * b[1] / n)), mn, mx, a[5]])
+
+
+def stats_from_moments(rows, kind):
+    """varI / stddevI / CVI / maxI / minI / span (`kind`: var, stddev, cv, max, min, span) from per-shard run-moment
+    vectors listed in genome order, with the reference's closing arithmetic (statistics.c:259,288-289,312-314;
+    wtamd_moments_finish): an empty genome gives what that gives (-0.0, NaN)."""
+    m = np.array([0.0, 0.0, 0.0, np.nan, np.nan, 0.0])
+    for r in rows:
+        m = merge_run_moments(m, r)
+    if kind in ("max", "min", "span"):
+        return float(m[{"max": 4, "min": 3, "span": 1}[kind]])
+    with np.errstate(all="ignore"):
+        res = m[2] / (m[1] - 1)
+        if kind == "var":
+            return float(res)
+        res = np.sqrt(res)
+        if kind == "stddev":
+            return float(res)
+        if kind in ("cv", "CV"):
+            return float(res / (m[0] / m[1]))
+    raise ValueError("unknown statistic %r" % kind)
+
+
 def allgather_moments(mine, group=None):
     """all_gather of one [n_items, 6] moment table per rank (rows a rank did not compute are zero)
     -> their sum, i.e. the full table (each row is computed by exactly one rank)."""
