@@ -1,15 +1,72 @@
 // wt_emu.cpp -- TEST INFRASTRUCTURE ONLY (never linked into the product).
 //
-// Phase-by-phase CPU emulation of the HIP kernels in
-// wiggletools_amd/csrc/wt_core.h: every __syncthreads()-delimited phase is run
-// for tid = 0..T-1 in turn, windows are executed in ticket order.  It exists so
-// that the alignment / reducer / look-back logic can be checked against the
-// oracle in the build container, which has no GPU.  Built by tests/emu/build.py
+// CPU emulation of the HIP kernels in wiggletools_amd/csrc (wt_engine.hip, wt_walk.hip; their logic: wt_core.h, wt_delta.h,
+// wt_walk.h, wt_mwalk.h): one emulated workgroup, windows in ticket order.  It exists so that the alignment / reducer /
+// look-back logic can be checked against the oracle in the build container, which has no GPU.  Built by tests/emu/build.py
 // into tests/emu/libwt_emu.so.
+//
+// ONE LOOP OVER THE LANES = ONE __syncthreads() INTERVAL OF THE KERNEL, no more and no fewer: the drivers below (EmuRun::run,
+// run_patch, run_delta, run_walk, run_mwalk) carry the kernels' phase calls and barriers in the kernels' order, and
+// tests/test_emu_skeleton.py compares the two texts.  Inside an interval the wavefronts run in the order WTEMU_WAVE_ORDER asks
+// for (forward | reverse | rotate:<k> | shuffle:<seed>, WaveSched below); tests/test_emu_wave_order.py holds every order to the
+// same bits.  An interval in which shared device code lets two wavefronts touch one LDS word, one of them writing, shows there.
+//
+// Intervals per kernel (lines of wt_engine.hip / wt_walk.hip at this commit; `a | b`: a loop boundary INSIDE the substitute of
+// one device call, see below; (c): only under the condition c):
+//
+//  wt_reduce_kernel (wt_engine.hip:55-201) = run()
+//   1  :90-93    ticket by lane 0, (NR) dflt32
+//   2  :100-102  header by lane 0, zero
+//   3+ :114-136  per chunk, a barrier after each: (MULTI, not the first) zero; [eval_init,] load; count_a; count_b; (FUSE) eval_chunk
+//   4  :138-141  (FUSE, two passes) eval_mid, emask
+//   5  :143-144  escan
+//   6  :149-184  publish by lane 0, (MULTIPLEX: complete by wave 0, barrier), every eval_chunk pass -- MULTI: zero, load,
+//                count_a, count_b, eval_chunk with a barrier after each --, eval_mid, eval_finish, (MWU without register columns:
+//                barrier, mwu_rank, barrier, mwu_tail), complete by wave 0
+//   7  :187-188  write
+//   8  :190-194  stats + next ticket by lane 0
+//  wt_patch_kernel (wt_engine.hip:512-593) = run_patch(): as 2-7 with a barrier in front of the header, without ticket, look-back
+//   and statistics; n_emit / goffset set by lane 0 at the head of 6, a barrier between eval_finish and write, none after write
+//  wt_delta_kernel (wt_engine.hip:225-471) = run_delta(); Sum / Mean follow the kernel's `else` branches, not EP (below)
+//   1  :255-265  ticket + header by lane 0, zero (WT_DELTA_ZERO_EARLY)
+//   2+ :280-360  per chunk, a barrier after each: ranges_w1 -> ranges1; ranges_w2 -> ranges2 | ranges3; pass_mm / pass1 / pass2.
+//                The verdicts (wt_delta_verdict, wt_delta_window_verdict) are read once, by the driver, where every lane reads
+//                them; mark_bad by lane 0 shares the interval that follows.  Redone window: barrier, rezero, barrier, passes again
+//   3  :364-393  scan_w1[_tt|_mm] -> scan1 | scan2, barrier, scan3[_tt|_mm], barrier, (TT) combine_tt, barrier
+//   4  :410-416  (TT) mark_bad by lane 0 on risk; escan_wave -> wt_phase_escan over wave 0's lanes + publish by lane 0; nextw by all
+//   5  :420-432  complete + note_offset by wave 0; (TT) tail_tt by the other waves; not TT: this is interval 7
+//   6  :434-435  (TT) load_res_tt                      <- the barrier after it is this file's first finding
+//   7  :437-439  stage
+//   8  :444-445  copy_out
+//   9  :450-460  stats + ticket + header by lane 0, zero by all
+//  wt_walk_kernel (wt_walk.hip:21-137) = run_walk()
+//   1  :40-46    ticket + header by lane 0, defaults
+//   2  :52-54    walk_zero, ranges_w1 -> ranges1
+//   3  :55-56    walk_ranges_w2 -> walk_ranges3
+//   4  :59-60    walk_pass
+//   5  :64-66    emits, scan_a
+//   6  :67-68    scan_b
+//   7  :70-78    publish by lane 0, walk_lane          (fallback :83-109: a barrier after each of offsets1, scan_b, offsets2, per
+//                round walk_pass and walk_lane, then scan_a and scan_b)
+//   8  :113-114  complete by wave 0
+//   9  :119-120  walk_write
+//   10 :124-130  stats + ticket + header by lane 0
+//  wt_mwalk_kernel (wt_walk.hip:143-215) = run_mwalk(): 1-4 as above; 5 :171-174 mwalk_events, mwalk_lane (fallback as above);
+//   6 :197-198 scan_a; 7 :199-200 scan_b; 8 :202-204 publish by lane 0, complete by wave 0; 9 :205-206 mwalk_write; 10 as above
+//
+// SUBSTITUTED (device-only wave code, `#ifndef WT_EMU`; what stands here instead is NOT vouched for by the wave-order tests -- only
+// the -m gpu parity tests cover the device flavour): wt_delta_ranges_w1 / _w2, wt_walk_ranges_w2, wt_delta_scan_w1 / _tt / _mm,
+// wt_delta_escan_wave (-> emu_escan_wave), wt_waves_before32 / 64 inside scan3*, the ballots of wt_delta_combine_tt, the wave
+// reductions of wt_delta_copy_out and its WT_DELTA_COPY2 form, wt_lookback_publish / _complete (restated below for one lane), and the
+// whole early-publish route of Sum / Mean (EP: wt_delta_scan3_cov / _val, wt_delta_stage_ep, wt_delta_note_offset_ep).
+// NOT PERMUTED: the stretch-walking rounds (emu_walk_lanes / emu_mwalk_lanes: wt_walk_lane / wt_mwalk_lane, the two lanes of a pair
+// as two real threads); they run after the other fragments of their interval, pairs ascending.  No interval is pinned to `forward`.
 #define WT_EMU 1
 #include <algorithm>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 #include <thread>
@@ -18,6 +75,76 @@
 #include "../../wiggletools_amd/csrc/wt_plan.h"
 
 namespace {
+
+// ---------------------------------------------------------------------------
+// The workgroup scheduler.  A driver below is written like the kernel it restates: ph(...) hands over what every lane does
+// next (a "fragment": one phase call, with the kernel's own `if (tid ...)` around it), barrier() stands where the kernel has
+// __syncthreads().  Nothing runs until the barrier: then the interval's fragments are run wave by wave in the order the run
+// asked for (WTEMU_WAVE_ORDER), inside a wave fragment by fragment with the lanes ascending -- a wavefront executes in
+// lockstep, and the WT_EMU stubs of the ballots rely on "lane 0 of a word first" (wt_delta_combine_tt).
+// ---------------------------------------------------------------------------
+struct WaveSched {
+    enum { FORWARD, REVERSE, ROTATE, SHUFFLE };
+    int mode = FORWARD;
+    unsigned long long arg = 0;         // rotate: the first wave; shuffle: the seed
+    unsigned long long n_interval = 0;  // counter of the counter-based generator: the permutation of interval i depends on (seed, i) alone
+    struct Frag { int n; std::function<void(int)> f; };
+    std::vector<Frag> pend;
+    std::vector<int> order;
+
+    // "forward" | "reverse" | "rotate:<k>" | "shuffle:<seed>"; false: not understood
+    bool parse(const char *s) {
+        mode = FORWARD; arg = 0;
+        if (!s || !*s || !strcmp(s, "forward")) return true;
+        if (!strcmp(s, "reverse")) { mode = REVERSE; return true; }
+        if (!strncmp(s, "rotate:", 7)) { mode = ROTATE; arg = strtoull(s + 7, nullptr, 10); return true; }
+        if (!strncmp(s, "shuffle:", 8)) { mode = SHUFFLE; arg = strtoull(s + 8, nullptr, 10); return true; }
+        return false;
+    }
+    static unsigned long long mix(unsigned long long x) {       // splitmix64's finaliser
+        x += 0x9E3779B97F4A7C15ull;
+        x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+        x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+        return x ^ (x >> 31);
+    }
+    void make_order(int nw) {
+        order.resize(nw);
+        for (int i = 0; i < nw; i++) order[i] = i;
+        if (nw < 2) return;
+        if (mode == REVERSE) std::reverse(order.begin(), order.end());
+        else if (mode == ROTATE) std::rotate(order.begin(), order.begin() + (int) (arg % (unsigned long long) nw), order.end());
+        else if (mode == SHUFFLE) {
+            const unsigned long long key = mix(arg ^ mix(n_interval));
+            for (int i = nw - 1; i > 0; i--) std::swap(order[i], order[(int) (mix(key + (unsigned long long) i) % (unsigned long long) (i + 1))]);
+        }
+    }
+    // one interval: every pending fragment over its lanes
+    void run() {
+        int nmax = 0;
+        for (const Frag &g : pend) nmax = std::max(nmax, g.n);
+        make_order((nmax + 63) / 64);
+        for (int w : order)
+            for (const Frag &g : pend)
+                for (int t = w * 64; t < std::min(g.n, w * 64 + 64); t++) g.f(t);
+        pend.clear();
+        n_interval++;
+    }
+};
+
+// The wave flavour of the look-back (wt_core.h, device only: ballots) restated for one lane: publish is the same two stores;
+// complete is the sequential walk over the predecessors' status words (wt_phase_lookback: windows run in ticket order here, so
+// every predecessor has its inclusive prefix out and the walk is one step).
+void wt_lookback_publish(const WtParams &P, WtCtx &c, long long k, unsigned long long mine) {
+    c.sh->n_emit = (int32_t) mine;
+    if (k > 0) wt_status_store(&P.status[k], WT_FLAG_AGG | mine);
+}
+void wt_lookback_publish(const WtParams &P, WtCtx &c, long long k) { wt_lookback_publish(P, c, k, (unsigned long long) c.epfx[P.n_words]); }
+void wt_lookback_complete(const WtParams &P, WtCtx &c, long long k, int lane, unsigned long long mine) {
+    if (lane == 0) wt_phase_lookback(P, c, k, mine);
+}
+void wt_lookback_complete(const WtParams &P, WtCtx &c, long long k, int lane) { wt_lookback_complete(P, c, k, lane, (unsigned long long) c.epfx[P.n_words]); }
+// wt_delta_escan_wave (device only: wave scans) for one lane of wave 0: the LDS-only scan over the 64 lanes
+void emu_escan_wave(const WtParams &P, WtCtx &c, int lane) { wt_phase_escan(P, c, lane, 64); }
 
 struct EmuRun {
     WtParams P;
@@ -29,82 +156,203 @@ struct EmuRun {
     struct PatchGroup { long long goff; std::vector<long long> wins; };
     bool patch = false;
     std::vector<PatchGroup> groups;
+    WaveSched S;
 
+    template <class F> void ph(int n, F f) { S.pend.push_back(WaveSched::Frag{n, std::function<void(int)>(f)}); }
+    void barrier() { S.run(); }             // where the kernel has __syncthreads()
+    void sub_barrier() { S.run(); }         // a loop boundary inside the substitute of ONE device call (see the table above)
+    void flush() { S.run(); }               // before a piece that the scheduler does not run (the stretch-walking rounds)
+
+    // wt_reduce_kernel
     template <int OP, class ValT, class ScrT, int K, bool MULTI, int NR = 0>
     void run() {
+        if (patch) { run_patch<OP, ValT, ScrT, K, MULTI, NR>(); return; }
         WtCtx c;
         wt_ctx_init(c, P, lds.data());
         std::vector<char> slab((size_t) (P.g_scratch_slab + P.g_attr_slab));
         if (P.g_scratch_slab) c.scratch = slab.data();      // one emulated workgroup: one slab
         if (P.g_attr_slab) c.attr = slab.data() + P.g_scratch_slab;
-        const int T = plan.T;
+        const int T = plan.T, nt = T;
+        std::vector<WtLane<K>> L(T);
+        std::vector<WtAcc<K, NR>> A(T);
+        ph(T, [&](int tid) { if (tid == 0) c.sh->ticket = (long long) wt_glb_add64(&P.counters[WT_CTR_TICKET], 1ull); });
         if (NR > 0)
-            for (int i = 0; i < P.n_tracks; i++) c.dflt32[i] = (float) P.defaults[i];
-        std::vector<WtLane<K>> lanes(T);
-        size_t gi = 0, wi = 0;
-        long long patch_goff = 0;
+            ph(T, [&](int tid) { for (int i = tid; i < P.n_tracks; i += nt) c.dflt32[i] = (float) P.defaults[i]; });
+        barrier();
         for (;;) {
-            long long k;
-            if (patch) {
-                while (gi < groups.size() && wi >= groups[gi].wins.size()) { gi++; wi = 0; }
-                if (gi >= groups.size()) break;
-                if (wi == 0) patch_goff = groups[gi].goff;
-                k = groups[gi].wins[wi++];
-            } else {
-                k = (long long) wt_glb_add64(&P.counters[WT_CTR_TICKET], 1ull);
-                if (k >= P.n_windows) break;
-            }
-            constexpr bool two = (OP == WT_OP_TTEST || OP == WT_OP_MWU);
+            const long long k = c.sh->ticket;
+            if (k >= P.n_windows) break;
+            ph(T, [&, k](int tid) { if (tid == 0) wt_phase_header(P, c, k); });
+            ph(T, [&](int tid) { wt_phase_zero(P, c, true, tid, nt); });
+            barrier();
+            const int N = P.n_tracks, NC = MULTI ? P.chunk_tracks : N, n_chunks = MULTI ? P.n_chunks : 1;
+            constexpr bool FUSE = MULTI && OP != WT_OP_MULTIPLEX;
             constexpr int npass = wt_eval_passes(OP);
-            const int N = P.n_tracks, NC = P.chunk_tracks;
-            constexpr bool multi = MULTI;
-            std::vector<WtAcc<K, NR>> acc(T);
-            constexpr bool fuse = MULTI && OP != WT_OP_MULTIPLEX;      // as in wt_reduce_kernel
-            wt_phase_header(P, c, k);
-            for (int t = 0; t < T; t++) wt_phase_zero(P, c, true, t, T);
-            for (int t = 0; t < T; t++) wt_eval_init<OP, K>(acc[t]);
-            for (int ch = 0; ch < P.n_chunks; ch++) {
-                const int t_lo = ch * NC, t_hi = std::min(N, t_lo + NC);
-                if (ch > 0) for (int t = 0; t < T; t++) wt_phase_zero(P, c, false, t, T);
-                for (int t = 0; t < T; t++) wt_phase_load<ValT>(P, c, t_lo, t_hi, true, t, T);
-                for (int t = 0; t < T; t++) wt_phase_count_a(P, c, t_lo, t_hi, t, T);
-                for (int t = 0; t < T; t++) wt_phase_count_b(P, c, t_lo, t_hi, t, T);
-                if (fuse) for (int t = 0; t < T; t++) wt_phase_eval_chunk<OP, ValT, ScrT, K>(P, c, acc[t], 0, t_lo, t_hi, true, t, T);
-            }
-            if (fuse && npass == 2) for (int t = 0; t < T; t++) wt_eval_mid<OP, K>(P, acc[t]);
-            for (int t = 0; t < T; t++) wt_phase_emask(P, c, two, t, T);
-            for (int t = 0; t < T; t++) wt_phase_escan(P, c, t, T);
-            if (patch) {                    // the difference-array kernel already placed this window's runs
-                c.sh->n_emit = (int32_t) c.epfx[P.n_words];
-                c.sh->goffset = patch_goff;
-                patch_goff += c.sh->n_emit;
-            } else {
-                wt_phase_lookback(P, c, k);     // sequential emulation: the offset is known at once
-            }
-            for (int pass = fuse ? 1 : 0; pass < npass; pass++) {
-                for (int ch = 0; ch < P.n_chunks; ch++) {
-                    const int t_lo = ch * NC, t_hi = std::min(N, t_lo + NC);
-                    if (multi) {
-                        for (int t = 0; t < T; t++) wt_phase_zero(P, c, false, t, T);
-                        for (int t = 0; t < T; t++) wt_phase_load<ValT>(P, c, t_lo, t_hi, false, t, T);
-                        for (int t = 0; t < T; t++) wt_phase_count_a(P, c, t_lo, t_hi, t, T);
-                        for (int t = 0; t < T; t++) wt_phase_count_b(P, c, t_lo, t_hi, t, T);
-                    }
-                    for (int t = 0; t < T; t++) wt_phase_eval_chunk<OP, ValT, ScrT, K>(P, c, acc[t], pass, t_lo, t_hi, false, t, T);
+            ph(T, [&](int tid) { wt_eval_init<OP, K>(A[tid]); });
+            for (int ch = 0; ch < n_chunks; ch++) {
+                const int t_lo = ch * NC, t_hi = (t_lo + NC < N) ? t_lo + NC : N;
+                if (MULTI && ch > 0) {
+                    ph(T, [&](int tid) { wt_phase_zero(P, c, false, tid, nt); });
+                    barrier();
                 }
-                if (pass == 0 && npass == 2) for (int t = 0; t < T; t++) wt_eval_mid<OP, K>(P, acc[t]);
+                ph(T, [&, t_lo, t_hi](int tid) { wt_phase_load<ValT>(P, c, t_lo, t_hi, true, tid, nt); });
+                barrier();
+                ph(T, [&, t_lo, t_hi](int tid) { wt_phase_count_a(P, c, t_lo, t_hi, tid, nt); });
+                barrier();
+                ph(T, [&, t_lo, t_hi](int tid) { wt_phase_count_b(P, c, t_lo, t_hi, tid, nt); });
+                barrier();
+                if (FUSE) {
+                    ph(T, [&, t_lo, t_hi](int tid) { wt_phase_eval_chunk<OP, ValT, ScrT, K>(P, c, A[tid], 0, t_lo, t_hi, true, tid, nt); });
+                    barrier();
+                }
             }
-            for (int t = 0; t < T; t++) wt_phase_eval_finish<OP, ValT, ScrT, K>(P, c, acc[t], lanes[t], t, T);
+            if (FUSE && npass == 2) ph(T, [&](int tid) { wt_eval_mid<OP, K>(P, A[tid]); });
+            ph(T, [&](int tid) { wt_phase_emask(P, c, OP == WT_OP_TTEST || OP == WT_OP_MWU, tid, nt); });
+            barrier();
+            ph(T, [&](int tid) { wt_phase_escan(P, c, tid, nt); });
+            barrier();
+            ph(T, [&, k](int tid) { if (tid == 0) wt_lookback_publish(P, c, k); });
+            if (OP == WT_OP_MULTIPLEX) {
+                ph(T, [&, k](int tid) { if (tid < 64) wt_lookback_complete(P, c, k, tid); });
+                barrier();
+            }
+            for (int pass = FUSE ? 1 : 0; pass < npass; pass++) {
+                for (int ch = 0; ch < n_chunks; ch++) {
+                    const int t_lo = ch * NC, t_hi = (t_lo + NC < N) ? t_lo + NC : N;
+                    if (MULTI) {
+                        ph(T, [&](int tid) { wt_phase_zero(P, c, false, tid, nt); });
+                        barrier();
+                        ph(T, [&, t_lo, t_hi](int tid) { wt_phase_load<ValT>(P, c, t_lo, t_hi, false, tid, nt); });
+                        barrier();
+                        ph(T, [&, t_lo, t_hi](int tid) { wt_phase_count_a(P, c, t_lo, t_hi, tid, nt); });
+                        barrier();
+                        ph(T, [&, t_lo, t_hi](int tid) { wt_phase_count_b(P, c, t_lo, t_hi, tid, nt); });
+                        barrier();
+                    }
+                    ph(T, [&, pass, t_lo, t_hi](int tid) { wt_phase_eval_chunk<OP, ValT, ScrT, K>(P, c, A[tid], pass, t_lo, t_hi, false, tid, nt); });
+                    if (MULTI) barrier();
+                }
+                if (pass == 0 && npass == 2) ph(T, [&](int tid) { wt_eval_mid<OP, K>(P, A[tid]); });
+            }
+            ph(T, [&](int tid) { wt_phase_eval_finish<OP, ValT, ScrT, K>(P, c, A[tid], L[tid], tid, nt); });
             if (OP == WT_OP_MWU && NR == 0) {
-                for (int t = 0; t < T; t++) wt_phase_mwu_rank<ScrT>(P, c, t, T);
-                for (int t = 0; t < T; t++) wt_phase_mwu_tail<K>(P, c, acc[t], lanes[t], t, T);
+                barrier();
+                ph(T, [&](int tid) { wt_phase_mwu_rank<ScrT>(P, c, tid, nt); });
+                barrier();
+                ph(T, [&](int tid) { wt_phase_mwu_tail<K>(P, c, A[tid], L[tid], tid, nt); });
             }
-            for (int t = 0; t < T; t++) wt_phase_write<OP, ValT, K>(P, c, lanes[t], t, T);
-            if (!patch) wt_window_stats(P, c);
+            ph(T, [&, k](int tid) { if (OP != WT_OP_MULTIPLEX && tid < 64) wt_lookback_complete(P, c, k, tid); });
+            barrier();
+            ph(T, [&](int tid) { wt_phase_write<OP, ValT, K>(P, c, L[tid], tid, nt); });
+            barrier();
+            ph(T, [&](int tid) {
+                if (tid == 0) {
+                    wt_window_stats(P, c);
+                    c.sh->ticket = (long long) wt_glb_add64(&P.counters[WT_CTR_TICKET], 1ull);
+                }
+            });
+            barrier();
         }
     }
 
-    // wt_walk_kernel, phase by phase
+    // wt_patch_kernel (one emulated workgroup takes the items one after the other)
+    template <int OP, class ValT, class ScrT, int K, bool MULTI, int NR>
+    void run_patch() {
+        WtCtx c;
+        wt_ctx_init(c, P, lds.data());
+        const int T = plan.T, nt = T;
+        std::vector<WtLane<K>> L(T);
+        std::vector<WtAcc<K, NR>> A(T);
+        if (NR > 0)
+            for (int i = 0; i < P.n_tracks; i++) c.dflt32[i] = (float) P.defaults[i];
+        const int N = P.n_tracks, NC = MULTI ? P.chunk_tracks : N, n_chunks = MULTI ? P.n_chunks : 1;
+        for (const PatchGroup &g : groups) {
+            const long long goff = g.goff;
+            for (const long long k : g.wins) {
+                barrier();
+                ph(T, [&, k](int tid) { if (tid == 0) wt_phase_header(P, c, k); });
+                ph(T, [&](int tid) { wt_phase_zero(P, c, true, tid, nt); });
+                barrier();
+                constexpr int npass = wt_eval_passes(OP);
+                ph(T, [&](int tid) { wt_eval_init<OP, K>(A[tid]); });
+                for (int cc = 0; cc < n_chunks; cc++) {
+                    const int t_lo = cc * NC, t_hi = (t_lo + NC < N) ? t_lo + NC : N;
+                    if (MULTI && cc > 0) {
+                        ph(T, [&](int tid) { wt_phase_zero(P, c, false, tid, nt); });
+                        barrier();
+                    }
+                    ph(T, [&, t_lo, t_hi](int tid) { wt_phase_load<ValT>(P, c, t_lo, t_hi, false, tid, nt); });
+                    barrier();
+                    ph(T, [&, t_lo, t_hi](int tid) { wt_phase_count_a(P, c, t_lo, t_hi, tid, nt); });
+                    barrier();
+                    ph(T, [&, t_lo, t_hi](int tid) { wt_phase_count_b(P, c, t_lo, t_hi, tid, nt); });
+                    barrier();
+                    if (MULTI) {
+                        ph(T, [&, t_lo, t_hi](int tid) { wt_phase_eval_chunk<OP, ValT, ScrT, K>(P, c, A[tid], 0, t_lo, t_hi, true, tid, nt); });
+                        barrier();
+                    }
+                }
+                if (MULTI && npass == 2) ph(T, [&](int tid) { wt_eval_mid<OP, K>(P, A[tid]); });
+                ph(T, [&](int tid) { wt_phase_emask(P, c, OP == WT_OP_TTEST, tid, nt); });
+                barrier();
+                ph(T, [&](int tid) { wt_phase_escan(P, c, tid, nt); });
+                barrier();
+                ph(T, [&, goff](int tid) {
+                    const long long n_emit = (long long) c.epfx[P.n_words];
+                    if (tid == 0) { c.sh->n_emit = (int32_t) n_emit; c.sh->goffset = goff; }
+                });
+                for (int pass = MULTI ? 1 : 0; pass < npass; pass++) {
+                    for (int cc = 0; cc < n_chunks; cc++) {
+                        const int t_lo = cc * NC, t_hi = (t_lo + NC < N) ? t_lo + NC : N;
+                        if (MULTI) {
+                            ph(T, [&](int tid) { wt_phase_zero(P, c, false, tid, nt); });
+                            barrier();
+                            ph(T, [&, t_lo, t_hi](int tid) { wt_phase_load<ValT>(P, c, t_lo, t_hi, false, tid, nt); });
+                            barrier();
+                            ph(T, [&, t_lo, t_hi](int tid) { wt_phase_count_a(P, c, t_lo, t_hi, tid, nt); });
+                            barrier();
+                            ph(T, [&, t_lo, t_hi](int tid) { wt_phase_count_b(P, c, t_lo, t_hi, tid, nt); });
+                            barrier();
+                        }
+                        ph(T, [&, pass, t_lo, t_hi](int tid) { wt_phase_eval_chunk<OP, ValT, ScrT, K>(P, c, A[tid], pass, t_lo, t_hi, false, tid, nt); });
+                        if (MULTI) barrier();
+                    }
+                    if (pass == 0 && npass == 2) ph(T, [&](int tid) { wt_eval_mid<OP, K>(P, A[tid]); });
+                }
+                ph(T, [&](int tid) { wt_phase_eval_finish<OP, ValT, ScrT, K>(P, c, A[tid], L[tid], tid, nt); });
+                barrier();
+                ph(T, [&](int tid) { wt_phase_write<OP, ValT, K>(P, c, L[tid], tid, nt); });
+            }
+        }
+        flush();        // (the kernel ends here: the last window's write)
+    }
+
+    // the stretch-walking rounds: the two lanes of a stretch run side by side as two real threads (they exchange values:
+    // wt_pair_xchg), one pair at a time, lanes ascending -- not the scheduler's
+    template <bool FIXED>
+    void emu_walk_lanes(WtCtx &c, WtWalkCtx &w, std::vector<WtWalkLane> &L, int l0, int l1, uint32_t ev0) {
+        const int T = plan.T;
+        if (!w.pair) {
+            for (int t = l0; t < l1; t++) wt_walk_lane<FIXED, false>(P, c, w, L[t], ev0, t, T);
+            return;
+        }
+        for (int q = l0; q < l1; q++) {
+            std::thread odd([&, q] { wt_walk_lane<FIXED, true>(P, c, w, L[2 * q + 1], ev0, 2 * q + 1, T); });
+            wt_walk_lane<FIXED, true>(P, c, w, L[2 * q], ev0, 2 * q, T);
+            odd.join();
+        }
+    }
+    template <bool FIXED>
+    void emu_mwalk_lanes(WtCtx &c, WtWalkCtx &w, std::vector<WtWalkLane> &L, int l0, int l1, uint32_t ev0) {
+        const int T = plan.T;
+        for (int q = l0; q < l1; q++) {
+            std::thread odd([&, q] { wt_mwalk_lane<FIXED>(P, c, w, L[2 * q + 1], ev0, 2 * q + 1, T); });
+            wt_mwalk_lane<FIXED>(P, c, w, L[2 * q], ev0, 2 * q, T);
+            odd.join();
+        }
+    }
+
+    // wt_walk_kernel
     void run_walk() {
         WtCtx c{};
         c.sh = (WtShared *) (lds.data() + P.off_shared);
@@ -113,61 +361,83 @@ struct EmuRun {
         std::vector<char> slab((size_t) P.g_scratch_slab + 64);
         WtWalkCtx w;
         wt_walk_ctx_init(w, P, lds.data(), slab.data());
-        const int T = plan.T;
-        for (int t = 0; t < T; t++) wt_walk_defaults(P, w, t, T);
+        const int T = plan.T, nt = T;
         std::vector<WtWalkLane> L(T);
+        ph(T, [&](int tid) {
+            if (tid == 0) {
+                const long long k0 = (long long) wt_glb_add64(&P.counters[WT_CTR_TICKET], 1ull);
+                c.sh->ticket = k0;
+                if (k0 < P.n_windows) wt_phase_header(P, c, k0);
+            }
+        });
+        ph(T, [&](int tid) { wt_walk_defaults(P, w, tid, nt); });
+        barrier();
         for (;;) {
-            const long long k = (long long) wt_glb_add64(&P.counters[WT_CTR_TICKET], 1ull);
+            const long long k = c.sh->ticket;
             if (k >= P.n_windows) break;
-            wt_phase_header(P, c, k);
-            for (int t = 0; t < T; t++) wt_walk_zero(P, c, w, t, T);
-            for (int t = 0; t < T; t++) wt_delta_ranges1(P, c, d, 0, t, T);
-            for (int t = 0; t < T; t++) wt_walk_ranges3(d, t, T);
-            for (int t = 0; t < T; t++) wt_walk_pass<false>(P, c, w, d, 0u, 0u, t, T);
-            for (int t = 0; t < T; t++) wt_walk_emits(P, c, w, L[t], t, T);
-            for (int t = 0; t < T; t++) wt_walk_scan_a(w, wt_walk_emit_count(w, L[t], t), t, T);
-            for (int t = 0; t < T; t++) wt_walk_scan_b(w, t, T);
-            const unsigned long long mine = w.base[T];
-            // pair mode: the two lanes of a stretch run side by side (they exchange values: wt_pair_xchg), one pair at a time
-            auto walk_lanes = [&](int l0, int l1, uint32_t ev0, bool fixed) {
-                if (!w.pair) {
-                    for (int t = l0; t < l1; t++) { if (fixed) wt_walk_lane<true, false>(P, c, w, L[t], ev0, t, T); else wt_walk_lane<false, false>(P, c, w, L[t], ev0, t, T); }
-                    return;
-                }
-                for (int q = l0; q < l1; q++) {
-                    std::thread odd([&, q] { if (fixed) wt_walk_lane<true, true>(P, c, w, L[2 * q + 1], ev0, 2 * q + 1, T); else wt_walk_lane<false, true>(P, c, w, L[2 * q + 1], ev0, 2 * q + 1, T); });
-                    if (fixed) wt_walk_lane<true, true>(P, c, w, L[2 * q], ev0, 2 * q, T); else wt_walk_lane<false, true>(P, c, w, L[2 * q], ev0, 2 * q, T);
-                    odd.join();
-                }
-            };
+            ph(T, [&](int tid) { wt_walk_zero(P, c, w, tid, nt); });
+            ph(T, [&](int tid) { wt_delta_ranges1(P, c, d, 0, tid, nt); });
+            barrier();
+            ph(T, [&](int tid) { wt_walk_ranges3(d, tid, nt); });
+            barrier();
+            ph(T, [&](int tid) { wt_walk_pass<false>(P, c, w, d, 0u, 0u, tid, nt); });
+            barrier();
+            ph(T, [&](int tid) { wt_walk_emits(P, c, w, L[tid], tid, nt); });
+            ph(T, [&](int tid) { wt_walk_scan_a(w, wt_walk_emit_count(w, L[tid], tid), tid, nt); });
+            barrier();
+            ph(T, [&](int tid) { wt_walk_scan_b(w, tid, nt); });
+            barrier();
+            const unsigned long long mine = w.base[nt];
+            ph(T, [&, k, mine](int tid) { if (tid == 0) wt_lookback_publish(P, c, k, mine); });
             if (w.novf[0] <= w.ov_cap) {
                 n_rounds++;
-                walk_lanes(0, w.nstr, 0u, true);
+                flush();
+                emu_walk_lanes<true>(c, w, L, 0, w.nstr, 0u);
+                barrier();
             } else {
                 n_fallback++;
-                for (int t = 0; t < T; t++) wt_walk_offsets1(P, w, t, T);
-                for (int t = 0; t < T; t++) wt_walk_scan_b(w, t, T);
-                for (int t = 0; t < T; t++) wt_walk_offsets2(P, w, t, T);
+                barrier();
+                ph(T, [&](int tid) { wt_walk_offsets1(P, w, tid, nt); });
+                barrier();
+                ph(T, [&](int tid) { wt_walk_scan_b(w, tid, nt); });
+                barrier();
+                ph(T, [&](int tid) { wt_walk_offsets2(P, w, tid, nt); });
+                barrier();
                 for (int l0 = 0; l0 < w.nstr;) {
-                    const int l1 = wt_walk_round_end(w, l0, T);
+                    const int l1 = wt_walk_round_end(w, l0, nt);
                     const uint32_t ev0 = w.base[l0 << w.pair], ev1 = w.base[l1 << w.pair];
                     if (ev1 > ev0) {
                         n_rounds++;
-                        for (int t = 0; t < T; t++) wt_walk_pass<true>(P, c, w, d, ev0, ev1, t, T);
-                        walk_lanes(l0, l1, ev0, false);
+                        ph(T, [&, ev0, ev1](int tid) { wt_walk_pass<true>(P, c, w, d, ev0, ev1, tid, nt); });
+                        barrier();
+                        emu_walk_lanes<false>(c, w, L, l0, l1, ev0);
+                        barrier();
                     }
                     l0 = l1;
                 }
-                for (int t = 0; t < T; t++) wt_walk_scan_a(w, wt_walk_emit_count(w, L[t], t), t, T);
-                for (int t = 0; t < T; t++) wt_walk_scan_b(w, t, T);
+                ph(T, [&](int tid) { wt_walk_scan_a(w, wt_walk_emit_count(w, L[tid], tid), tid, nt); });
+                barrier();
+                ph(T, [&](int tid) { wt_walk_scan_b(w, tid, nt); });
+                barrier();
             }
             if ((unsigned long long) w.base[T] != mine) { fprintf(stderr, "wtemu: walking kernel: run count changed\n"); abort(); }
-            wt_phase_lookback(P, c, k, (unsigned long long) w.base[T]);
-            for (int t = 0; t < T; t++) wt_walk_write(P, c, w, L[t], t, T);
-            wt_window_stats(P, c);
+            ph(T, [&, k, mine](int tid) { if (tid < 64) wt_lookback_complete(P, c, k, tid, mine); });
+            barrier();
+            ph(T, [&](int tid) { wt_walk_write(P, c, w, L[tid], tid, nt); });
+            barrier();
+            ph(T, [&](int tid) {
+                if (tid == 0) {
+                    wt_window_stats(P, c);
+                    const long long kn = (long long) wt_glb_add64(&P.counters[WT_CTR_TICKET], 1ull);
+                    c.sh->ticket = kn;
+                    if (kn < P.n_windows) wt_phase_header(P, c, kn);
+                }
+            });
+            barrier();
         }
     }
-    // wt_mwalk_kernel, phase by phase (the two lanes of a stretch side by side: they exchange values, wt_pair_xchg)
+
+    // wt_mwalk_kernel
     void run_mwalk() {
         WtCtx c{};
         c.sh = (WtShared *) (lds.data() + P.off_shared);
@@ -176,53 +446,79 @@ struct EmuRun {
         std::vector<char> slab((size_t) P.g_scratch_slab + 64);
         WtWalkCtx w;
         wt_walk_ctx_init(w, P, lds.data(), slab.data());
-        const int T = plan.T;
-        for (int t = 0; t < T; t++) wt_walk_defaults(P, w, t, T);
+        const int T = plan.T, nt = T;
         std::vector<WtWalkLane> L(T);
+        ph(T, [&](int tid) {
+            if (tid == 0) {
+                const long long k0 = (long long) wt_glb_add64(&P.counters[WT_CTR_TICKET], 1ull);
+                c.sh->ticket = k0;
+                if (k0 < P.n_windows) wt_phase_header(P, c, k0);
+            }
+        });
+        ph(T, [&](int tid) { wt_walk_defaults(P, w, tid, nt); });
+        barrier();
         for (;;) {
-            const long long k = (long long) wt_glb_add64(&P.counters[WT_CTR_TICKET], 1ull);
+            const long long k = c.sh->ticket;
             if (k >= P.n_windows) break;
-            wt_phase_header(P, c, k);
-            for (int t = 0; t < T; t++) wt_walk_zero(P, c, w, t, T);
-            for (int t = 0; t < T; t++) wt_delta_ranges1(P, c, d, 0, t, T);
-            for (int t = 0; t < T; t++) wt_walk_ranges3(d, t, T);
-            for (int t = 0; t < T; t++) wt_walk_pass<false>(P, c, w, d, 0u, 0u, t, T);
-            for (int t = 0; t < T; t++) wt_mwalk_events(P, c, w, L[t], t, T);
-            auto walk_lanes = [&](int l0, int l1, uint32_t ev0, bool fixed) {
-                for (int q = l0; q < l1; q++) {
-                    std::thread odd([&, q] { if (fixed) wt_mwalk_lane<true>(P, c, w, L[2 * q + 1], ev0, 2 * q + 1, T); else wt_mwalk_lane<false>(P, c, w, L[2 * q + 1], ev0, 2 * q + 1, T); });
-                    if (fixed) wt_mwalk_lane<true>(P, c, w, L[2 * q], ev0, 2 * q, T); else wt_mwalk_lane<false>(P, c, w, L[2 * q], ev0, 2 * q, T);
-                    odd.join();
-                }
-            };
+            ph(T, [&](int tid) { wt_walk_zero(P, c, w, tid, nt); });
+            ph(T, [&](int tid) { wt_delta_ranges1(P, c, d, 0, tid, nt); });
+            barrier();
+            ph(T, [&](int tid) { wt_walk_ranges3(d, tid, nt); });
+            barrier();
+            ph(T, [&](int tid) { wt_walk_pass<false>(P, c, w, d, 0u, 0u, tid, nt); });
+            barrier();
+            ph(T, [&](int tid) { wt_mwalk_events(P, c, w, L[tid], tid, nt); });
             if (w.novf[0] <= w.ov_cap) {
                 n_rounds++;
-                walk_lanes(0, w.nstr, 0u, true);
+                flush();
+                emu_mwalk_lanes<true>(c, w, L, 0, w.nstr, 0u);
+                barrier();
             } else {
                 n_fallback++;
-                for (int t = 0; t < T; t++) wt_walk_offsets1(P, w, t, T);
-                for (int t = 0; t < T; t++) wt_walk_scan_b(w, t, T);
-                for (int t = 0; t < T; t++) wt_walk_offsets2(P, w, t, T);
+                barrier();
+                ph(T, [&](int tid) { wt_walk_offsets1(P, w, tid, nt); });
+                barrier();
+                ph(T, [&](int tid) { wt_walk_scan_b(w, tid, nt); });
+                barrier();
+                ph(T, [&](int tid) { wt_walk_offsets2(P, w, tid, nt); });
+                barrier();
                 for (int l0 = 0; l0 < w.nstr;) {
-                    const int l1 = wt_walk_round_end(w, l0, T);
+                    const int l1 = wt_walk_round_end(w, l0, nt);
                     const uint32_t ev0 = w.base[l0 << 1], ev1 = w.base[l1 << 1];
                     if (ev1 > ev0) {
                         n_rounds++;
-                        for (int t = 0; t < T; t++) wt_walk_pass<true>(P, c, w, d, ev0, ev1, t, T);
-                        walk_lanes(l0, l1, ev0, false);
+                        ph(T, [&, ev0, ev1](int tid) { wt_walk_pass<true>(P, c, w, d, ev0, ev1, tid, nt); });
+                        barrier();
+                        emu_mwalk_lanes<false>(c, w, L, l0, l1, ev0);
+                        barrier();
                     }
                     l0 = l1;
                 }
             }
-            for (int t = 0; t < T; t++) wt_walk_scan_a(w, wt_walk_emit_count(w, L[t], t), t, T);
-            for (int t = 0; t < T; t++) wt_walk_scan_b(w, t, T);
-            wt_phase_lookback(P, c, k, (unsigned long long) w.base[T]);
-            for (int t = 0; t < T; t++) wt_mwalk_write(P, c, w, L[t], t, T);
-            wt_window_stats(P, c);
+            ph(T, [&](int tid) { wt_walk_scan_a(w, wt_walk_emit_count(w, L[tid], tid), tid, nt); });
+            barrier();
+            ph(T, [&](int tid) { wt_walk_scan_b(w, tid, nt); });
+            barrier();
+            const unsigned long long mine = w.base[nt];
+            ph(T, [&, k, mine](int tid) { if (tid == 0) wt_lookback_publish(P, c, k, mine); });
+            ph(T, [&, k, mine](int tid) { if (tid < 64) wt_lookback_complete(P, c, k, tid, mine); });
+            barrier();
+            ph(T, [&](int tid) { wt_mwalk_write(P, c, w, L[tid], tid, nt); });
+            barrier();
+            ph(T, [&](int tid) {
+                if (tid == 0) {
+                    wt_window_stats(P, c);
+                    const long long kn = (long long) wt_glb_add64(&P.counters[WT_CTR_TICKET], 1ull);
+                    c.sh->ticket = kn;
+                    if (kn < P.n_windows) wt_phase_header(P, c, kn);
+                }
+            });
+            barrier();
         }
     }
     long long n_rounds = 0, n_fallback = 0;
 
+    // wt_delta_kernel (Sum / Mean: its `else` branches -- the early publish of the device, EP, is wave code throughout)
     template <int OP, bool DF = false>
     void run_delta() {
         constexpr bool TT = OP == WT_OP_TTEST;      // two sets per position (wt_delta_scan3_tt)
@@ -232,91 +528,173 @@ struct EmuRun {
         wt_ctx_init(c, P, lds.data());
         WtDeltaCtx d;
         wt_delta_ctx_init(d, P, lds.data());
-        const int T = plan.T;
-        std::vector<WtDeltaLane> dl(T);
-        std::vector<WtDeltaLane2> dl2(T);
+        const int T = plan.T, nt = T;
+        std::vector<WtDeltaLane> DL(T);
+        std::vector<WtDeltaLane2> DL2(T);
         std::vector<int32_t> wc_mm(T, 0);
+        std::vector<WtLane<WT_DELTA_K>> L(T);
+        const int nts = QQ ? P.W / WT_DELTA_K : nt;
         int guess = 0;      // the workgroup's unit exponent (0: none yet)
-        std::vector<WtLane<WT_DELTA_K>> lanes(T);
+        unsigned long long mine = 0;        // (wave 0's, uniform)
+        auto scan_lane = [&](int tid) { return !QQ || tid < nts; };     // WT_SCAN_LANE
+        ph(T, [&](int tid) {
+            if (tid == 0) {
+                const long long k0 = (long long) wt_glb_add64(&P.counters[WT_CTR_TICKET], 1ull);
+                c.sh->ticket = k0;
+                if (k0 < P.n_windows) wt_phase_header(P, c, k0);
+            }
+        });
+        if constexpr (MM) ph(T, [&](int tid) { wt_delta_zero_mm<OP == WT_OP_MAX>(P, c, d, tid, nt); });
+        else ph(T, [&](int tid) { wt_delta_zero<QQ, TT>(P, c, d, tid, nt); });
+        barrier();
         for (;;) {
-            const long long k = (long long) wt_glb_add64(&P.counters[WT_CTR_TICKET], 1ull);
+            const long long k = c.sh->ticket;
             if (k >= P.n_windows) break;
-            wt_phase_header(P, c, k);
-            if constexpr (MM) { for (int t = 0; t < T; t++) wt_delta_zero_mm<OP == WT_OP_MAX>(P, c, d, t, T); }
-            else for (int t = 0; t < T; t++) wt_delta_zero<QQ, TT>(P, c, d, t, T);
-            const int nchunks = (P.n_tracks + T - 1) / T;
-            auto ranges = [&](int ch) {
-                for (int t = 0; t < T; t++) wt_delta_ranges1(P, c, d, ch * T, t, T);
-                for (int t = 0; t < T; t++) wt_delta_ranges2(P, c, d, t, T);
-                for (int t = 0; t < T; t++) wt_delta_ranges3(P, c, d, t, T);
-            };
+            const int nchunks = (P.n_tracks + nt - 1) / nt;
+            auto ntr = [&](int ch) { const int r = P.n_tracks - ch * nt; return r < nt ? r : nt; };     // tracks of chunk ch
             int scale = 1;
             if constexpr (MM) {
                 for (int ch = 0; ch < nchunks; ch++) {
-                    ranges(ch);
-                    for (int t = 0; t < T; t++) wt_delta_pass_mm<OP == WT_OP_MAX>(P, c, d, t, T);
+                    ph(T, [&, ch](int tid) { wt_delta_ranges1(P, c, d, ch * nt, tid, nt); });
+                    barrier();
+                    ph(T, [&](int tid) { wt_delta_ranges2(P, c, d, tid, nt); });
+                    sub_barrier();
+                    ph(T, [&](int tid) { wt_delta_ranges3(P, c, d, tid, nt); });
+                    barrier();
+                    ph(T, [&](int tid) { wt_delta_pass_mm<OP == WT_OP_MAX>(P, c, d, tid, nt); });
+                    barrier();
                 }
-                if (d.dsh->bad) wt_delta_mark_bad(P, c, k);
-            } else if (guess == 0) {       // no unit exponent known yet: range pass, then the delta pass
+                ph(T, [&, k](int tid) { if (tid == 0 && d.dsh->bad) wt_delta_mark_bad(P, c, k); });
+            } else if (guess == 0) {
                 for (int ch = 0; ch < nchunks; ch++) {
-                    ranges(ch);
-                    for (int t = 0; t < T; t++) wt_delta_pass1(P, c, d, t, T);
+                    ph(T, [&, ch](int tid) { wt_delta_ranges1(P, c, d, ch * nt, tid, nt); });
+                    barrier();
+                    ph(T, [&](int tid) { wt_delta_ranges2(P, c, d, tid, nt); });
+                    sub_barrier();
+                    ph(T, [&](int tid) { wt_delta_ranges3(P, c, d, tid, nt); });
+                    barrier();
+                    ph(T, [&](int tid) { wt_delta_pass1(P, c, d, tid, nt); });
+                    barrier();
                 }
                 const bool any = d.dsh->emin <= d.dsh->emax;
                 const bool ok = wt_delta_verdict(P, d, scale);
-                if (!ok) wt_delta_mark_bad(P, c, k);
+                ph(T, [&, k, ok](int tid) { if (!ok && tid == 0) wt_delta_mark_bad(P, c, k); });
                 for (int ch = 0; ch < nchunks; ch++) {
-                    if (nchunks > 1) ranges(ch);
-                    for (int t = 0; t < T; t++) wt_delta_pass2<QQ, DF, TT>(P, c, d, scale, ok, false, true, t, T, std::min(T, P.n_tracks - ch * T), ch * T);
+                    if (nchunks > 1) {
+                        ph(T, [&, ch](int tid) { wt_delta_ranges1(P, c, d, ch * nt, tid, nt); });
+                        barrier();
+                        ph(T, [&](int tid) { wt_delta_ranges2(P, c, d, tid, nt); });
+                        sub_barrier();
+                        ph(T, [&](int tid) { wt_delta_ranges3(P, c, d, tid, nt); });
+                        barrier();
+                    }
+                    const int ntr_ch = ntr(ch);
+                    ph(T, [&, scale, ok, ch, ntr_ch](int tid) { wt_delta_pass2<QQ, DF, TT>(P, c, d, scale, ok, false, true, tid, nt, ntr_ch, ch * nt); });
+                    barrier();
                 }
                 if (any && ok) guess = scale;
-            } else {                // speculative single pass with the workgroup's unit
+            } else {
                 for (int ch = 0; ch < nchunks; ch++) {
-                    ranges(ch);
-                    for (int t = 0; t < T; t++) wt_delta_pass2<QQ, DF, TT>(P, c, d, guess, true, true, true, t, T, std::min(T, P.n_tracks - ch * T), ch * T);
+                    ph(T, [&, ch](int tid) { wt_delta_ranges1(P, c, d, ch * nt, tid, nt); });
+                    barrier();
+                    ph(T, [&](int tid) { wt_delta_ranges2(P, c, d, tid, nt); });
+                    sub_barrier();
+                    ph(T, [&](int tid) { wt_delta_ranges3(P, c, d, tid, nt); });
+                    barrier();
+                    const int ntr_ch = ntr(ch);
+                    ph(T, [&, guess, ch, ntr_ch](int tid) { wt_delta_pass2<QQ, DF, TT>(P, c, d, guess, true, true, true, tid, nt, ntr_ch, ch * nt); });
+                    barrier();
                 }
-                int lo; bool ok;
+                int lo;
+                bool ok;
                 scale = guess;
                 if (!wt_delta_window_verdict(P, d, guess, lo, ok)) {
                     if (!ok) {
-                        wt_delta_mark_bad(P, c, k);         // (values rewritten by the patch; the structure is in place)
+                        ph(T, [&, k](int tid) { if (tid == 0) wt_delta_mark_bad(P, c, k); });
                     } else {
                         n_redo++;
-                        for (int t = 0; t < T; t++) wt_delta_rezero<QQ, TT>(P, c, d, t, T);
+                        barrier();
+                        ph(T, [&](int tid) { wt_delta_rezero<QQ, TT>(P, c, d, tid, nt); });
+                        barrier();
                         for (int ch = 0; ch < nchunks; ch++) {
-                            if (nchunks > 1) ranges(ch);
-                            for (int t = 0; t < T; t++) wt_delta_pass2<QQ, DF, TT>(P, c, d, lo, ok, false, false, t, T, std::min(T, P.n_tracks - ch * T), ch * T);
+                            if (nchunks > 1) {
+                                ph(T, [&, ch](int tid) { wt_delta_ranges1(P, c, d, ch * nt, tid, nt); });
+                                barrier();
+                                ph(T, [&](int tid) { wt_delta_ranges2(P, c, d, tid, nt); });
+                                sub_barrier();
+                                ph(T, [&](int tid) { wt_delta_ranges3(P, c, d, tid, nt); });
+                                barrier();
+                            }
+                            const int ntr_ch = ntr(ch);
+                            ph(T, [&, lo, ok, ch, ntr_ch](int tid) { wt_delta_pass2<QQ, DF, TT>(P, c, d, lo, ok, false, false, tid, nt, ntr_ch, ch * nt); });
+                            barrier();
                         }
                         scale = lo;
                         guess = lo;
                     }
                 }
             }
-            const int TS = P.W / WT_DELTA_K;        // the scans' lanes (wt_delta_kernel: nts)
             if constexpr (TT) {
-                for (int t = 0; t < 2 * TS; t++) wt_delta_scan1_tt(P, c, d, dl2[t], t, TS);
-                for (int t = 0; t < 2 * TS; t++) wt_delta_scan2_tt(P, c, d, t, TS);
-                for (int t = 0; t < 2 * TS; t++) wt_delta_scan3_tt(P, c, d, dl2[t], scale, t, TS);
-                for (int t = 0; t < T; t++) wt_delta_combine_tt(P, c, d, t, T);
-                for (int t = 0; t < T; t++) wt_delta_tail_tt(P, d, t, T);
-                if (d.dsh->risk && c.sh->bad_slot < 0) wt_delta_mark_bad(P, c, k);
+                ph(T, [&](int tid) { if (tid < 2 * nts) wt_delta_scan1_tt(P, c, d, DL2[tid], tid, nts); });
+                sub_barrier();
+                ph(T, [&](int tid) { if (tid < 2 * nts) wt_delta_scan2_tt(P, c, d, tid, nts); });
+                barrier();
+                ph(T, [&, scale](int tid) { if (tid < 2 * nts) wt_delta_scan3_tt(P, c, d, DL2[tid], scale, tid, nts); });
+                barrier();
+                ph(T, [&](int tid) { wt_delta_combine_tt(P, c, d, tid, nt); });
+                barrier();
+                ph(T, [&, k](int tid) { if (tid == 0 && d.dsh->risk && c.sh->bad_slot < 0) wt_delta_mark_bad(P, c, k); });
             } else if constexpr (MM) {
-                for (int t = 0; t < TS; t++) wt_delta_scan1_mm(P, c, d, wc_mm[t], t, TS);
-                for (int t = 0; t < TS; t++) wt_delta_scan2_mm(P, c, d, t, TS);
-                for (int t = 0; t < TS; t++) wt_delta_scan3_mm<OP == WT_OP_MAX>(P, c, d, 0, lanes[t], t, TS);
+                ph(T, [&](int tid) { wt_delta_scan1_mm(P, c, d, wc_mm[tid], tid, nt); });
+                sub_barrier();
+                ph(T, [&](int tid) { wt_delta_scan2_mm(P, c, d, tid, nt); });
+                barrier();
+                ph(T, [&](int tid) { wt_delta_scan3_mm<OP == WT_OP_MAX>(P, c, d, 0, L[tid], tid, nt); });
+                barrier();
             } else {
-                for (int t = 0; t < TS; t++) wt_delta_scan1<QQ>(P, c, d, dl[t], t, TS);
-                for (int t = 0; t < TS; t++) wt_delta_scan2<QQ>(P, c, d, t, TS);
-                for (int t = 0; t < TS; t++) wt_delta_scan3<OP>(P, c, d, dl[t], lanes[t], scale, t, TS);
+                ph(T, [&](int tid) { if (scan_lane(tid)) wt_delta_scan1<QQ>(P, c, d, DL[tid], tid, nts); });
+                sub_barrier();
+                ph(T, [&](int tid) { if (scan_lane(tid)) wt_delta_scan2<QQ>(P, c, d, tid, nts); });
+                barrier();
+                ph(T, [&, scale](int tid) { if (scan_lane(tid)) wt_delta_scan3<OP>(P, c, d, DL[tid], L[tid], scale, tid, nts); });
+                barrier();
             }
-            for (int t = 0; t < T; t++) wt_delta_nextw(P, c, t, T);
-            for (int t = 0; t < T; t++) wt_phase_escan(P, c, t, T);
-            wt_phase_lookback(P, c, k);
-            for (int t = 0; t < WT_BAD_SUB; t++) wt_delta_note_offset(P, c, t);
-            if constexpr (TT) for (int t = 0; t < TS; t++) wt_delta_load_res_tt(P, d, lanes[t], t);
-            for (int t = 0; t < TS; t++) wt_delta_stage<OP>(P, c, d, lanes[t], t, TS);
-            for (int t = 0; t < T; t++) wt_delta_copy_out(P, c, d, t, T);
-            wt_window_stats(P, c);
+            ph(T, [&](int tid) { if (tid < 64) emu_escan_wave(P, c, tid); });
+            ph(T, [&, k](int tid) {
+                if (tid < 64) {
+                    mine = (unsigned long long) c.epfx[P.n_words];
+                    if (tid == 0) wt_lookback_publish(P, c, k, mine);
+                }
+            });
+            ph(T, [&](int tid) { wt_delta_nextw(P, c, tid, nt); });
+            barrier();
+            ph(T, [&, k](int tid) {
+                if (tid < 64) {
+                    wt_lookback_complete(P, c, k, tid, mine);
+                    wt_delta_note_offset(P, c, tid);
+                }
+            });
+            if constexpr (TT) {
+                ph(T, [&](int tid) { if (tid >= 64) wt_delta_tail_tt(P, d, tid - 64, nt - 64); });
+                barrier();
+                ph(T, [&](int tid) { if (tid < nts) wt_delta_load_res_tt(P, d, L[tid], tid); });
+                barrier();
+            }
+            ph(T, [&](int tid) { if (scan_lane(tid)) wt_delta_stage<OP>(P, c, d, L[tid], tid, nts); });
+            barrier();
+            ph(T, [&](int tid) { wt_delta_copy_out(P, c, d, tid, nt); });
+            barrier();
+            ph(T, [&](int tid) {
+                if (tid == 0) {
+                    wt_window_stats(P, c);
+                    const long long kn = (long long) wt_glb_add64(&P.counters[WT_CTR_TICKET], 1ull);
+                    c.sh->ticket = kn;
+                    if (kn < P.n_windows) wt_phase_header(P, c, kn);
+                }
+            });
+            if constexpr (MM) ph(T, [&](int tid) { wt_delta_zero_mm<OP == WT_OP_MAX>(P, c, d, tid, nt); });
+            else ph(T, [&](int tid) { wt_delta_zero<QQ, TT>(P, c, d, tid, nt); });
+            barrier();
         }
     }
 };
@@ -343,6 +721,7 @@ long long wtemu_reduce(int n_chrom, int n_tracks, const int64_t *seg_off, const 
     long long used_delta = 0, delta_bad = 0, n_redo_total = 0, patched = 0, walk_used = 0, walk_rounds = 0, walk_fallback = 0;
     std::vector<int32_t> bad_list;
     std::vector<long long> bad_goff;
+    const char *wave_order = getenv("WTEMU_WAVE_ORDER");        // the order of the wavefronts inside every barrier interval (WaveSched)
     WtWindowTables delta_tab;
     int delta_W = 0;
     std::vector<unsigned long long> delta_counters;
@@ -352,6 +731,7 @@ long long wtemu_reduce(int n_chrom, int n_tracks, const int64_t *seg_off, const 
         const bool delta = attempt == 0 && o_tile == nullptr && wt_delta_eligible(op, value_is_f64 != 0, n_tracks, defaults);
         if (attempt == 0 && !delta) continue;
         EmuRun R;
+        if (!R.S.parse(wave_order)) { fprintf(stderr, "wtemu: WTEMU_WAVE_ORDER=%s not understood\n", wave_order); return -12; }
         std::string err;
         if (delta) wt_make_delta_plan_for(R.plan, n_tracks, op);
         else {

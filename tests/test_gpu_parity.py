@@ -493,6 +493,25 @@ def test_gpu_difference_array_ttest(oracle, engine, seed):
 
 
 @pytest.mark.gpu
+def test_gpu_difference_array_ttest_dense_windows(oracle, engine):
+    """wt_delta_kernel<ttest> where its staging reaches the top of acc[]: 100 tracks, 50 v 50, a breakpoint at every position, so
+    that nearly every 2048-bp window holds 1987 runs or more and WT_STAGE_AT (r + r / 32) places the last of them at acc[W ..] -- over
+    the p-values of the window's first positions, which wave 0 must have loaded by then (the barrier after wt_delta_load_res_tt;
+    tests/test_emu_wave_order.py shows what happens without it).  A run on the device cannot force the bad order; this makes sure the
+    shape where the order matters is exercised by every run of the suite."""
+    from wiggletools_amd.runlists import synth
+    t = synth(100, [330000], mean_run=1.0, seed=3, gap_prob=0.0, dtype=np.float32, value_levels=800)
+    ts = engine.TrackSet.from_runlists(t)
+    got = ts.reduce_host("ttest", n_set0=50)
+    st = ts.stats()
+    assert st["kernel"] == 1 and st["window_bp"] == 2048, st
+    per_window = np.bincount(got[1] // 2048)
+    assert len(per_window) >= 150 and (per_window >= 1987).sum() >= 0.9 * len(per_window), (len(per_window), int((per_window >= 1987).sum()))
+    assert_runs_equal(got, oracle.reduce(t.as_dict(), "ttest", n_set0=50), 1e-9, "ttest, dense windows %s" % st)
+    ts.close()
+
+
+@pytest.mark.gpu
 def test_gpu_difference_array_ttest_vs_general_kernel(oracle, engine, monkeypatch):
     """The two routes of TTestReduction on the same 100 tracks x 300 kbp (50 v 50, the shape of the bench record): coordinates
     equal, values equal bit for bit (k/8 values: neither route's sums round); and the second launch -- verdict known, no

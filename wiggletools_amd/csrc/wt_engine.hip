@@ -424,11 +424,15 @@ __global__ void __launch_bounds__(WT_DELTA_SQ(OP) ? WT_DELTA_SQ_BLOCK : WT_DELTA
         WT_TICK(6);
         if constexpr (TT) {
             // two-sample launches: the Student tail of every emitted position is what the look-back of wave 0 overlaps -- the other
-            // wavefronts share the window's positions (the staging needs their results: one more barrier)
+            // wavefronts share the window's positions.  Two barriers before the staging: the first, because a scan lane's 8 results
+            // were written by other wavefronts' lanes (wt_delta_tail_tt); the second, because the staging reuses what the results
+            // lie in -- with the spare entries of WT_STAGE_AT, run number 1986 and later of a 2048-bp window are staged at
+            // acc[W ..], the results of the window's first positions, which their own lanes must have loaded by then
             if (tid >= 64) wt_delta_tail_tt(P, d, tid - 64, nt - 64);
             __syncthreads();
             WT_TICK(2);             // (profile builds: the tail, less the look-back, in the slot of the exponent-range pass)
             if (tid < nts) wt_delta_load_res_tt(P, d, L, tid);
+            __syncthreads();
         }
         if constexpr (EP) wt_delta_stage_ep<OP>(P, c, d, L, ep_em, DL.evmask, ep_rank, tid, nts);
         else if (WT_SCAN_LANE) wt_delta_stage<OP>(P, c, d, L, tid, nts);
