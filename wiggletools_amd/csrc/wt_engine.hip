@@ -842,10 +842,15 @@ __global__ void wt_auc_final_kernel(const double *partial, int n, double *out) {
 // Pearson correlation of two tracks over the Multiplexer tile (reference PearsonIntegrator,
 // statistics.c:414-465).  The reference updates {count, sum, T_XX, T_XY, T_YY} run by run with the
 // weighted Welford / Chan step (its `new_mean` is old sum / new count; expanding
-// n*L/(n+L) * (X - mean)^2 gives exactly its expression).  Here every lane applies that very step
-// to a contiguous slice of runs, and slices are merged pairwise in genome order with the same
-// formula for two aggregates -- mathematically identical, rounding differs in the last bits
-// (tests: 1e-9 relative against the oracle; the reference prints 6 decimals).
+// n*L/(n+L) * (X - mean)^2 gives exactly its expression).  Here every lane applies that step IN ITS
+// UNEXPANDED FORM, n*L/(n+L) * (X - mean)^2, to a contiguous slice of runs, and slices are merged
+// pairwise in genome order with the same formula for two aggregates -- mathematically identical.
+// The expanded form sums terms of size mean^2 to get one of size deviation^2; in the reference's one long
+// pass that costs (mean/deviation)^2 of the digits with errors of either sign, but at the start of
+// every slice -- 65 536 of them, n / (n + L) far from 1 -- the errors are biased: on a track of
+// relative variance 1e-10 (70 001 runs) T_XX came out 2.1e-8 off where the reference's own pass is
+// 4.9e-10 off; unexpanded it is 2.9e-13 off (tests/test_side_kernels.py::test_gpu_pearson_constant_track_rule,
+// against exact rational arithmetic; the other tests hold 1e-9 against the oracle).
 // ---------------------------------------------------------------------------
 struct WtMoments {
     double n, sx, sy, txx, txy, tyy;
@@ -853,13 +858,11 @@ struct WtMoments {
 
 __device__ inline void wt_moments_add_run(WtMoments &m, double X, double Y, double L) {
     if (m.n > 0) {
-        const double nn = m.n + L;
-        const double old_mx = m.sx / m.n, new_mx = m.sx / nn;
-        const double old_my = m.sy / m.n, new_my = m.sy / nn;
-        const double ratio = m.n / nn;
-        m.txy += (new_mx * old_my + ratio * X * Y - new_mx * Y - new_my * X) * L;
-        m.txx += (new_mx * (old_mx - 2 * X) + ratio * X * X) * L;
-        m.tyy += (new_my * (old_my - 2 * Y) + ratio * Y * Y) * L;
+        const double dx = X - m.sx / m.n, dy = Y - m.sy / m.n;
+        const double w = m.n * L / (m.n + L);
+        m.txx += dx * dx * w;
+        m.txy += dx * dy * w;
+        m.tyy += dy * dy * w;
     }
     m.n += L;
     m.sx += X * L;
