@@ -1,8 +1,9 @@
 // wt_emu.cpp -- TEST INFRASTRUCTURE ONLY (never linked into the product).
 //
-// CPU emulation of the HIP kernels in wiggletools_amd/csrc (wt_engine.hip, wt_walk.hip; their logic: wt_core.h, wt_delta.h,
-// wt_walk.h, wt_mwalk.h): one emulated workgroup, windows in ticket order.  It exists so that the alignment / reducer /
-// look-back logic can be checked against the oracle in the build container, which has no GPU.  Built by tests/emu/build.py
+// CPU emulation of the HIP kernels in wiggletools_amd/csrc (wt_reduce_kernel.h, wt_patch_kernels.hip, wt_delta_kernel.h,
+// wt_walk.hip; their logic: wt_core.h, wt_delta.h, wt_walk.h, wt_mwalk.h): one emulated workgroup, windows in ticket order.  It
+// exists so that the alignment / reducer / look-back logic can be checked against the oracle in the build container, which has
+// no GPU.  Built by tests/emu/build.py
 // into tests/emu/libwt_emu.so.
 //
 // ONE LOOP OVER THE LANES = ONE __syncthreads() INTERVAL OF THE KERNEL, no more and no fewer: the drivers below (EmuRun::run,
@@ -11,48 +12,37 @@
 // for (forward | reverse | rotate:<k> | shuffle:<seed>, WaveSched below); tests/test_emu_wave_order.py holds every order to the
 // same bits.  An interval in which shared device code lets two wavefronts touch one LDS word, one of them writing, shows there.
 //
-// Intervals per kernel (lines of wt_engine.hip / wt_walk.hip at this commit; `a | b`: a loop boundary INSIDE the substitute of
-// one device call, see below; (c): only under the condition c):
+// Intervals per kernel, by phase name (tests/test_emu_skeleton.py holds them to the kernels' text; `a | b`: a loop boundary INSIDE
+// the substitute of one device call, see below; (c): only under the condition c):
 //
-//  wt_reduce_kernel (wt_engine.hip:55-201) = run()
-//   1  :90-93    ticket by lane 0, (NR) dflt32
-//   2  :100-102  header by lane 0, zero
-//   3+ :114-136  per chunk, a barrier after each: (MULTI, not the first) zero; [eval_init,] load; count_a; count_b; (FUSE) eval_chunk
-//   4  :138-141  (FUSE, two passes) eval_mid, emask
-//   5  :143-144  escan
-//   6  :149-184  publish by lane 0, (MULTIPLEX: complete by wave 0, barrier), every eval_chunk pass -- MULTI: zero, load,
-//                count_a, count_b, eval_chunk with a barrier after each --, eval_mid, eval_finish, (MWU without register columns:
-//                barrier, mwu_rank, barrier, mwu_tail), complete by wave 0
-//   7  :187-188  write
-//   8  :190-194  stats + next ticket by lane 0
-//  wt_patch_kernel (wt_engine.hip:512-593) = run_patch(): as 2-7 with a barrier in front of the header, without ticket, look-back
+//  wt_reduce_kernel (wt_reduce_kernel.h) = run()
+//   1  ticket by lane 0, (NR) dflt32;  2  header by lane 0, zero
+//   3+ per chunk, a barrier after each: (MULTI, not the first) zero; [eval_init,] load; count_a; count_b; (FUSE) eval_chunk
+//   4  (FUSE, two passes) eval_mid, emask;  5  escan
+//   6  publish by lane 0, (MULTIPLEX: complete by wave 0, barrier), every eval_chunk pass -- MULTI: zero, load,
+//       count_a, count_b, eval_chunk with a barrier after each --, eval_mid, eval_finish, (MWU without register columns:
+//       barrier, mwu_rank, barrier, mwu_tail), complete by wave 0
+//   7  write;  8  stats + next ticket by lane 0
+//  wt_patch_kernel (wt_patch_kernels.hip) = run_patch(): as 2-7 with a barrier in front of the header, without ticket, look-back
 //   and statistics; n_emit / goffset set by lane 0 at the head of 6, a barrier between eval_finish and write, none after write
-//  wt_delta_kernel (wt_engine.hip:225-471) = run_delta(); Sum / Mean follow the kernel's `else` branches, not EP (below)
-//   1  :255-265  ticket + header by lane 0, zero (WT_DELTA_ZERO_EARLY)
-//   2+ :280-360  per chunk, a barrier after each: ranges_w1 -> ranges1; ranges_w2 -> ranges2 | ranges3; pass_mm / pass1 / pass2.
-//                The verdicts (wt_delta_verdict, wt_delta_window_verdict) are read once, by the driver, where every lane reads
-//                them; mark_bad by lane 0 shares the interval that follows.  Redone window: barrier, rezero, barrier, passes again
-//   3  :364-393  scan_w1[_tt|_mm] -> scan1 | scan2, barrier, scan3[_tt|_mm], barrier, (TT) combine_tt, barrier
-//   4  :410-416  (TT) mark_bad by lane 0 on risk; escan_wave -> wt_phase_escan over wave 0's lanes + publish by lane 0; nextw by all
-//   5  :420-432  complete + note_offset by wave 0; (TT) tail_tt by the other waves; not TT: this is interval 7
-//   6  :434-435  (TT) load_res_tt                      <- the barrier after it is this file's first finding
-//   7  :437-439  stage
-//   8  :444-445  copy_out
-//   9  :450-460  stats + ticket + header by lane 0, zero by all
-//  wt_walk_kernel (wt_walk.hip:21-137) = run_walk()
-//   1  :40-46    ticket + header by lane 0, defaults
-//   2  :52-54    walk_zero, ranges_w1 -> ranges1
-//   3  :55-56    walk_ranges_w2 -> walk_ranges3
-//   4  :59-60    walk_pass
-//   5  :64-66    emits, scan_a
-//   6  :67-68    scan_b
-//   7  :70-78    publish by lane 0, walk_lane          (fallback :83-109: a barrier after each of offsets1, scan_b, offsets2, per
-//                round walk_pass and walk_lane, then scan_a and scan_b)
-//   8  :113-114  complete by wave 0
-//   9  :119-120  walk_write
-//   10 :124-130  stats + ticket + header by lane 0
-//  wt_mwalk_kernel (wt_walk.hip:143-215) = run_mwalk(): 1-4 as above; 5 :171-174 mwalk_events, mwalk_lane (fallback as above);
-//   6 :197-198 scan_a; 7 :199-200 scan_b; 8 :202-204 publish by lane 0, complete by wave 0; 9 :205-206 mwalk_write; 10 as above
+//  wt_delta_kernel (wt_delta_kernel.h) = run_delta(); Sum / Mean follow the kernel's `else` branches, not EP (below)
+//   1  ticket + header by lane 0, zero (WT_DELTA_ZERO_EARLY)
+//   2+ per chunk, a barrier after each: ranges_w1 -> ranges1; ranges_w2 -> ranges2 | ranges3; pass_mm / pass1 / pass2.
+//       The verdicts (wt_delta_verdict, wt_delta_window_verdict) are read once, by the driver, where every lane reads
+//       them; mark_bad by lane 0 shares the interval that follows.  Redone window: barrier, rezero, barrier, passes again
+//   3  scan_w1[_tt|_mm] -> scan1 | scan2, barrier, scan3[_tt|_mm], barrier, (TT) combine_tt, barrier
+//   4  (TT) mark_bad by lane 0 on risk; escan_wave -> wt_phase_escan over wave 0's lanes + publish by lane 0; nextw by all
+//   5  complete + note_offset by wave 0; (TT) tail_tt by the other waves; not TT: this is interval 7
+//   6  (TT) load_res_tt                      <- the barrier after it is this file's first finding
+//   7  stage;  8  copy_out;  9  stats + ticket + header by lane 0, zero by all
+//  wt_walk_kernel (wt_walk.hip) = run_walk()
+//   1  ticket + header by lane 0, defaults;  2  walk_zero, ranges_w1 -> ranges1;  3  walk_ranges_w2 -> walk_ranges3
+//   4  walk_pass;  5  emits, scan_a;  6  scan_b
+//   7  publish by lane 0, walk_lane          (fallback: a barrier after each of offsets1, scan_b, offsets2, per
+//       round walk_pass and walk_lane, then scan_a and scan_b)
+//   8  complete by wave 0;  9  walk_write;  10  stats + ticket + header by lane 0
+//  wt_mwalk_kernel (wt_walk.hip) = run_mwalk(): 1-4 as above; 5 mwalk_events, mwalk_lane (fallback as above);
+//   6 scan_a; 7 scan_b; 8 publish by lane 0, complete by wave 0; 9 mwalk_write; 10 as above
 //
 // SUBSTITUTED (device-only wave code, `#ifndef WT_EMU`; what stands here instead is NOT vouched for by the wave-order tests -- only
 // the -m gpu parity tests cover the device flavour): wt_delta_ranges_w1 / _w2, wt_walk_ranges_w2, wt_delta_scan_w1 / _tt / _mm,

@@ -27,9 +27,9 @@ EMU_NAMES = {"emu_walk_lanes": "wt_walk_lane", "emu_mwalk_lanes": "wt_mwalk_lane
 IGNORE = {"wt_ctx_init", "wt_delta_ctx_init", "wt_walk_ctx_init", "wt_glb_add64", "wt_eval_passes", "wt_lds"}
 DEFINED = {"WT_DELTA_ZERO_EARLY": 1}        # every other macro of an #if / #ifdef inside a kernel body is off (WT_PROFILE*, WT_MARK*)
 KERNELS = [
-    ("wt_reduce_kernel", "wt_engine.hip", "int NR = 0>\n    void run()"),       # (not WaveSched::run)
-    ("wt_patch_kernel", "wt_engine.hip", "void run_patch()"),
-    ("wt_delta_kernel", "wt_engine.hip", "void run_delta()"),
+    ("wt_reduce_kernel", "wt_reduce_kernel.h", "int NR = 0>\n    void run()"),       # (not WaveSched::run)
+    ("wt_patch_kernel", "wt_patch_kernels.hip", "void run_patch()"),
+    ("wt_delta_kernel", "wt_delta_kernel.h", "void run_delta()"),
     ("wt_walk_kernel", "wt_walk.hip", "void run_walk()"),
     ("wt_mwalk_kernel", "wt_walk.hip", "void run_mwalk()"),
 ]
@@ -178,7 +178,7 @@ def test_emulator_driver_has_the_kernels_phases_and_barriers(name, src, head):
 
 def test_a_removed_barrier_is_noticed():
     """the comparison itself: the delta kernel's text less one __syncthreads() (the one after wt_delta_load_res_tt) is red, and names it"""
-    kern, emu = kernel_sequence("wt_delta_kernel", "wt_engine.hip"), emulator_sequence("void run_delta()")
+    kern, emu = kernel_sequence("wt_delta_kernel", "wt_delta_kernel.h"), emulator_sequence("void run_delta()")
     i = kern.index("wt_delta_load_res_tt")
     assert kern[i + 1] == "BARRIER"
     msg = compare("wt_delta_kernel", kern[:i + 1] + kern[i + 2:], emu)

@@ -1,4 +1,4 @@
-# compares engine variants (csrc/build.py build_engine_variant) on the same box: C2 whole genome, kernel ms
+# compares kernel variants (csrc/build.py build_source_variant over KERNEL_SRCS + wt_engine.hip) on the same box: C2 whole genome, kernel ms
 # usage: tools/variants.sh <name> ...   ("-" = the default library)
 for v in "$@"; do
   L=$PWD/wiggletools_amd/csrc/libwiggletools_amd.so

@@ -1,7 +1,7 @@
 // wt_core.h -- the "bitmap multiplexer": window-local breakpoint alignment +
 // per-run reducers.  This header is the single source of the kernel logic.  It
 // is compiled
-//   * by hipcc for gfx950 inside wt_engine.hip (the product), and
+//   * by hipcc for gfx950 inside the kernel units (wt_kernels.h) and wt_engine.hip (the product), and
 //   * by g++ with -DWT_EMU inside tests/emu/wt_emu.cpp, a phase-by-phase CPU
 //     emulator of ONE workgroup used only by the `-m "not gpu"` tests to check
 //     the algorithm against the oracle in a container that has no GPU.
@@ -1167,7 +1167,7 @@ WT_DEV bool wt_gather_regs(const WtParams &P, const WtCtx &c, int p0, uint32_t *
 
 #if defined(WT_PROFILE) && !defined(WT_EMU)
 // -DWT_PROFILE builds: cycles of the register-column reducers' sub-phases (lane 0 of every wave)
-__device__ unsigned long long wt_prof2[8];
+static __device__ unsigned long long wt_prof2[8];       // (a copy per translation unit: read where it is written, wt_reduce_order.hip)
 #define WT_SUBTICK(slot) do { if ((threadIdx.x & 63) == 0) { const unsigned long long t_ = __builtin_readcyclecounter(); \
         atomicAdd(&wt_prof2[slot], t_ - wt_sub_t); wt_sub_t = t_; } } while (0)
 #define WT_SUBTICK_BEGIN unsigned long long wt_sub_t = __builtin_readcyclecounter()
@@ -1967,6 +1967,33 @@ WT_DEV void wt_index_apply(const WtParams &P, WtIndexCursor &c, long long g, int
     for (long long m = m_lo; m <= m_hi; m++) P.widx[(size_t) (c.rowbase + m) * N + c.i] = (uint32_t) jr;
     if (last)
         for (long long m = m_hi + 1; m <= c.nw; m++) P.widx[(size_t) (c.rowbase + m) * N + c.i] = (uint32_t) (jr + 1);
+}
+
+// first x in [lo, hi) with fin[x] >= b (hi if none), starting from a guess g in [lo, hi)
+WT_DEV long long wt_lane_lower_bound(const int32_t *fin, long long lo, long long hi, long long g, long long b) {
+    if (lo >= hi) return lo;
+    if ((long long) fin[g] >= b) {
+        hi = g;
+        for (long long d = 1;; d <<= 1) {
+            const long long q = hi - d;
+            if (q < lo) break;
+            if ((long long) fin[q] < b) { lo = q + 1; break; }
+            hi = q;
+        }
+    } else {
+        lo = g + 1;
+        for (long long d = 1;; d <<= 1) {
+            const long long q = lo + d - 1;
+            if (q >= hi) break;
+            if ((long long) fin[q] >= b) { hi = q; break; }
+            lo = q + 1;
+        }
+    }
+    while (lo < hi) {
+        const long long mid = (lo + hi) >> 1;
+        if ((long long) fin[mid] < b) lo = mid + 1; else hi = mid;
+    }
+    return lo;
 }
 
 #include "wt_delta.h"

@@ -1,15 +1,10 @@
-// wt_engine.hip -- gfx950 kernels + the bulk C ABI (wtamd_*) of
-// include/wiggletools_amd.h.  Compiled only by hipcc --offload-arch=gfx950.
+// wt_engine.hip -- the bulk C ABI (wtamd_*) of include/wiggletools_amd.h: planner glue, launches, the patch / probe state
+// machine, the small kernels below and -- included at the end -- the pipeline (wt_pipe.h).  The reducing kernels live in units
+// of their own behind wt_kernels.h.  Compiled only by hipcc --offload-arch=gfx950.
 //
 // Kernels
 //   wt_index_kernel     window index (widx): contiguous span of input runs per block, 4 per lane
-//   wt_reduce_kernel    persistent workgroups, one alignment window per ticket:
-//                       bitmap multiplexer + per-run reducer + ordered output
-//                       (logic in wt_core.h) -- every reducer, any track count
-//   wt_delta_kernel     Sum / Mean over float tracks: exact difference array, O(input runs)
-//                       (logic in wt_delta.h)
-//   wt_patch_kernel     the bitmap multiplexer over just the windows wt_delta_kernel could not
-//                       prove exact
+//   wt_index_coarse_kernel / wt_index_search_kernel   the same index by search
 //   wt_extents_kernel   first start / last finish per (chrom, track) segment
 //   wt_validate_kernel  input contract (sorted, non-overlapping, positive length)
 //   wt_auc_kernel       sum (finish-start)*value (+ span) over a run list (AUC, meanI)
@@ -24,7 +19,6 @@
 #include <unistd.h>
 #include <cstring>
 #include <map>
-#include <tuple>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -32,570 +26,13 @@
 #include "../../include/wiggletools_amd.h"
 #include "wt_core.h"
 #include "wt_plan.h"
+#include "wt_kernels.h"
 #include "wt_devscope.h"
 #include "wt_bwdev_core.h"
-
-#define WT_MAX_BLOCK 512
-// minimum waves per SIMD the register allocator must leave room for (MI355X_MICROARCH:
-// w = k*T/256).  Measured on MI355X: the K=4 kernels sit at 129 VGPRs unconstrained -- one
-// register over the limit for two 512-lane workgroups per CU -- so they are held to 128
-// (w = 4: 2.35 vs 3.14 ms on the bench kernel); the K=1 kernels fit anyway and schedule
-// better unconstrained (var/500 tracks: 71 vs 93 ms).
-#ifndef WT_MIN_WAVES
-#define WT_MIN_WAVES(K) ((K) == 4 ? 4 : 3)
-#endif
 
 // ---------------------------------------------------------------------------
 // kernels
 // ---------------------------------------------------------------------------
-template <int OP, class ValT, class ScrT, int K, bool MULTI, int NR>
-// (register columns, NR > 0: 256 lanes; the column + the exchange network's temporaries need more
-//  than the 168 VGPRs three waves per SIMD leave -- with that bound the compiler spilled 250
-//  registers into the middle of the network -- so NR = 128 runs two waves per SIMD, NR = 64 three)
-__global__ void __launch_bounds__(NR > 0 ? 256 : WT_MAX_BLOCK, NR > 0 ? (NR > 64 ? 2 : (NR > 32 ? 3 : 4)) : WT_MIN_WAVES(K)) wt_reduce_kernel(const WtParams P) {
-    extern __shared__ __attribute__((aligned(16))) char wt_lds[];
-    WtCtx c;
-    wt_ctx_init(c, P, wt_lds);
-    // global slab of this workgroup: [value columns, if they do not fit LDS][MWU attributes]
-    const size_t slab = (size_t) P.g_scratch_slab + (size_t) P.g_attr_slab;
-    if (MULTI && (OP == WT_OP_MEDIAN || OP == WT_OP_MWU) && P.g_scratch_slab)
-        c.scratch = P.g_scratch + (size_t) blockIdx.x * slab;
-    if (OP == WT_OP_MWU) c.attr = P.g_scratch + (size_t) blockIdx.x * slab + (size_t) P.g_scratch_slab;
-    WtLane<K> L;
-    const int tid = threadIdx.x, nt = blockDim.x;
-#ifdef WT_MARK_ONLY
-#define WT_MARK(x) do { if ((x) == WT_MARK_ONLY && (tid & 63) == 0) { P.debug[2 + (tid >> 6)] = (unsigned long long) (x); __threadfence_system(); } } while (0)
-#elif defined(WT_DEBUG_MARK)
-#define WT_MARK(x) do { if ((tid & 63) == 0) { if (tid == 0) { P.debug[0] = (unsigned long long) (x); P.debug[1] = (unsigned long long) k_dbg; } P.debug[2 + (tid >> 6)] = (unsigned long long) (x); __threadfence_system(); } } while (0)
-#else
-#define WT_MARK(x) do { } while (0)
-#endif
-#ifdef WT_PROFILE
-#define WT_TICK(slot) do { if (tid == 0) { const unsigned long long t_ = __builtin_readcyclecounter(); \
-        prof[slot] += t_ - t_last; t_last = t_; } } while (0)
-    unsigned long long prof[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long t_last = __builtin_readcyclecounter();
-#else
-#define WT_TICK(slot) do { } while (0)
-#endif
-    long long k_dbg = -1;
-    (void) k_dbg;
-    // Window tickets.  The lane-0 work at the end of one iteration (statistics) and at the start of
-    // the next (ticket) must NOT be left adjacent across the loop back-edge: hipcc (ROCm 7.2) merges
-    // the two `tid == 0` regions into a divergent exit of an inner loop, whose header -- including
-    // its s_barrier -- the other 63 lanes of wave 0 then re-enter before lane 0 has fetched the next
-    // ticket: every wave re-reads the stale ticket and the workgroup never terminates (observed on
-    // MI355X; any instruction between the two regions hides it).  So the next ticket is taken in the
-    // same lane-0 block as the statistics, followed by the barrier that publishes it.
-    if (tid == 0) c.sh->ticket = (long long) wt_glb_add64(&P.counters[WT_CTR_TICKET], 1ull);
-    if (NR > 0)
-        for (int i = tid; i < P.n_tracks; i += nt) c.dflt32[i] = (float) P.defaults[i];
-    __syncthreads();
-    for (;;) {
-        WT_MARK(1);
-        const long long k = c.sh->ticket;
-        k_dbg = k;
-        WT_MARK(2);
-        if (k >= P.n_windows) break;
-        if (tid == 0) wt_phase_header(P, c, k);
-        wt_phase_zero(P, c, true, tid, nt);
-        __syncthreads();
-        WT_TICK(0);
-        // pass A: every track's breakpoints and coverage enter U / cover[]; with one chunk the
-        // per-track bitmaps stay resident for the evaluation
-        const int N = P.n_tracks, NC = MULTI ? P.chunk_tracks : N, n_chunks = MULTI ? P.n_chunks : 1;
-        // Chunked tracks: every sweep over the chunks rebuilds their bitmaps, so the first
-        // evaluation pass is fused into the sweep that builds U / the coverage summaries (one
-        // sweep saved: sum-like ops 2 -> 1, var / stddev / CV 3 -> 2).  Not for the Multiplexer
-        // tile, whose rows need the look-back offset first.
-        constexpr bool FUSE = MULTI && OP != WT_OP_MULTIPLEX;
-        constexpr int npass = wt_eval_passes(OP);
-        WtAcc<K, NR> A;
-        wt_eval_init<OP, K>(A);
-        for (int ch = 0; ch < n_chunks; ch++) {
-            const int t_lo = ch * NC, t_hi = (t_lo + NC < N) ? t_lo + NC : N;
-            if (MULTI && ch > 0) {
-                wt_phase_zero(P, c, false, tid, nt);
-                __syncthreads();
-            }
-            WT_MARK(3);
-            wt_phase_load<ValT>(P, c, t_lo, t_hi, true, tid, nt);
-            __syncthreads();
-            WT_TICK(1);
-            WT_MARK(4);
-            wt_phase_count_a(P, c, t_lo, t_hi, tid, nt);
-            __syncthreads();
-            WT_MARK(5);
-            wt_phase_count_b(P, c, t_lo, t_hi, tid, nt);
-            __syncthreads();
-            WT_TICK(2);
-            if (FUSE) {     // first evaluation pass rides on this sweep (every position: E is not known yet)
-                wt_phase_eval_chunk<OP, ValT, ScrT, K>(P, c, A, 0, t_lo, t_hi, true, tid, nt);
-                __syncthreads();
-                WT_TICK(4);
-            }
-        }
-        if (FUSE && npass == 2) wt_eval_mid<OP, K>(P, A);
-        WT_MARK(6);
-        wt_phase_emask(P, c, OP == WT_OP_TTEST || OP == WT_OP_MWU, tid, nt);
-        __syncthreads();
-        WT_MARK(7);
-        wt_phase_escan(P, c, tid, nt);
-        __syncthreads();
-        WT_TICK(3);
-        // the window's run count is known before the reducers run: publish it now, so that no
-        // successor ever waits for our evaluation
-        WT_MARK(8);
-        if (tid == 0) wt_lookback_publish(P, c, k);
-        if (OP == WT_OP_MULTIPLEX) {     // the tile rows are written by the evaluation: offset first
-            if (tid < 64) wt_lookback_complete(P, c, k, tid);
-            __syncthreads();
-        }
-        WT_MARK(9);
-#pragma unroll
-        for (int pass = FUSE ? 1 : 0; pass < npass; pass++) {
-            for (int ch = 0; ch < n_chunks; ch++) {
-                const int t_lo = ch * NC, t_hi = (t_lo + NC < N) ? t_lo + NC : N;
-                if (MULTI) {
-                    wt_phase_zero(P, c, false, tid, nt);
-                    __syncthreads();
-                    wt_phase_load<ValT>(P, c, t_lo, t_hi, false, tid, nt);
-                    __syncthreads();
-                    wt_phase_count_a(P, c, t_lo, t_hi, tid, nt);
-                    __syncthreads();
-                    wt_phase_count_b(P, c, t_lo, t_hi, tid, nt);
-                    __syncthreads();
-                }
-                wt_phase_eval_chunk<OP, ValT, ScrT, K>(P, c, A, pass, t_lo, t_hi, false, tid, nt);
-                if (MULTI) __syncthreads();     // the next chunk overwrites the bitmaps
-            }
-            if (pass == 0 && npass == 2) wt_eval_mid<OP, K>(P, A);
-        }
-        wt_phase_eval_finish<OP, ValT, ScrT, K>(P, c, A, L, tid, nt);
-        if (OP == WT_OP_MWU && NR == 0) {      // the value columns are complete: rank with every lane, then the tie scan
-            __syncthreads();
-            wt_phase_mwu_rank<ScrT>(P, c, tid, nt);
-            __syncthreads();
-            wt_phase_mwu_tail<K>(P, c, A, L, tid, nt);
-        }
-        WT_TICK(4);
-        WT_MARK(10);
-        if (OP != WT_OP_MULTIPLEX && tid < 64) wt_lookback_complete(P, c, k, tid);
-        __syncthreads();
-        WT_TICK(5);
-        WT_MARK(11);
-        wt_phase_write<OP, ValT, K>(P, c, L, tid, nt);
-        __syncthreads();
-        WT_MARK(12);
-        if (tid == 0) {
-            wt_window_stats(P, c);
-            c.sh->ticket = (long long) wt_glb_add64(&P.counters[WT_CTR_TICKET], 1ull);
-        }
-        __syncthreads();
-        WT_TICK(6);
-    }
-#ifdef WT_PROFILE
-    if (tid == 0)
-        for (int q = 0; q < 8; q++) wt_glb_add64(&P.counters[WT_CTR_PROF + q], prof[q]);
-#endif
-}
-
-// Exact difference-array path for Sum / Mean over float tracks (wt_delta.h): O(intervals) work
-// instead of O(tracks x runs); LDS independent of the track count.
-// (var / stddev / CV also accumulate the sum of squares: 512 lanes, one workgroup per CU)
-#define WT_DELTA_SQ(OP) ((OP) == WT_OP_VAR || (OP) == WT_OP_STDDEV || (OP) == WT_OP_ENTROPY || (OP) == WT_OP_CV || (OP) == WT_OP_TTEST)
-#ifndef WT_DELTA_MIN_WAVES
-#define WT_DELTA_MIN_WAVES 4     // waves per SIMD the register allocation aims at (experiments: 6 spills, see DESIGN A.1)
-#endif
-#ifndef WT_DELTA_SQ_BLOCK
-#define WT_DELTA_SQ_BLOCK WT_DELTA_SQ_T0   // workgroup of the launches that also accumulate squares (768: three wavefronts per SIMD, 168 registers; the scans: the first 512 lanes, see wt_make_delta_plan)
-#endif
-#ifndef WT_DELTA_ZERO_EARLY
-#define WT_DELTA_ZERO_EARLY 1      // the accumulators are zeroed beside lane 0's ticket + header chain (0: at the window's start, rounds 1-5): -2 % at every density
-#endif
-#ifndef WT_DELTA_EARLY_PUBLISH
-#define WT_DELTA_EARLY_PUBLISH 1
-#endif
-#ifndef WT_DELTA_BLOCK
-#define WT_DELTA_BLOCK 1024     // (launch bound; the plan's default, see wt_make_delta_plan)
-#endif
-// DF: some track's default is non-zero (Sum / Mean; P.delta_df)
-// U: runs per lane and tile of the pass (round 6: 4, or 2 for launches whose windows hold few tiles per wavefront -- wt_launch_delta)
-template <int OP, bool DF = false, int U = WT_DELTA_U>
-__global__ void __launch_bounds__(WT_DELTA_SQ(OP) ? WT_DELTA_SQ_BLOCK : WT_DELTA_BLOCK, WT_DELTA_SQ(OP) ? 3 : WT_DELTA_MIN_WAVES) wt_delta_kernel(const WtParams P) {
-    extern __shared__ __attribute__((aligned(16))) char wt_lds[];
-    WtCtx c;
-    wt_ctx_init(c, P, wt_lds);
-    WtDeltaCtx d;
-    wt_delta_ctx_init(d, P, wt_lds);
-    constexpr bool QQ = WT_DELTA_SQ(OP);
-    constexpr bool TT = OP == WT_OP_TTEST;      // two sets per position (wt_delta_scan3_tt)
-    constexpr bool MM = OP == WT_OP_MAX || OP == WT_OP_MIN;     // range updates of a segment tree (wt_delta_apply_mm)
-    constexpr bool EP = WT_DELTA_EARLY_PUBLISH && (OP == WT_OP_SUM || OP == WT_OP_MEAN);       // the run count is published before the values are computed (wt_delta_scan3_cov / _val)
-    WtDeltaLane DL;
-    WtDeltaLane2 DL2;
-    (void) DL; (void) DL2;
-    WtLane<WT_DELTA_K> L;
-    uint32_t ep_rank = 0, ep_em = 0;        // EP: the lane's first rank among the window's emitted runs, its emitted byte
-    (void) ep_rank; (void) ep_em;
-    const int tid = threadIdx.x, nt = blockDim.x;
-    // lanes of the scans and the staging (8 positions each): all of them -- or, with squares, the first 512 of 1024.  (Sum / Mean must not
-    // see a run-time bound here: the guard alone cost wt_delta_kernel<mean> 31 more spilled registers and a quarter more HBM traffic.)
-    const int nts = QQ ? P.W / WT_DELTA_K : nt;
-#define WT_SCAN_LANE (!QQ || tid < nts)
-    int guess = 0;              // the workgroup's unit exponent (0: none yet); uniform across the lanes
-    long long k_dbg = -1;
-    (void) k_dbg;
-#ifdef WT_PROFILE
-    unsigned long long prof[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long t_last = __builtin_readcyclecounter();
-#endif
-    // ticket handling: see wt_reduce_kernel; lane 0 also prepares the next window's header there,
-    // so that the first phase of a window needs no barrier of its own
-    if (tid == 0) {
-        const long long k0 = (long long) wt_glb_add64(&P.counters[WT_CTR_TICKET], 1ull);
-        c.sh->ticket = k0;
-        if (k0 < P.n_windows) wt_phase_header(P, c, k0);
-    }
-#if WT_DELTA_ZERO_EARLY
-    // (experiment: the accumulators are zeroed beside lane 0's ticket + header chain, before the barrier that publishes the header)
-    if constexpr (MM) wt_delta_zero_mm<OP == WT_OP_MAX>(P, c, d, tid, nt);
-    else wt_delta_zero<QQ, TT>(P, c, d, tid, nt);
-#endif
-    __syncthreads();
-    for (;;) {
-        WT_MARK(101);
-        const long long k = c.sh->ticket;
-        k_dbg = k;
-        if (k >= P.n_windows) break;
-        const int nchunks = (P.n_tracks + nt - 1) / nt;
-        auto ntr = [&](int ch) { const int r = P.n_tracks - ch * nt; return r < nt ? r : nt; };     // tracks of chunk ch
-#if !WT_DELTA_ZERO_EARLY
-        if constexpr (MM) wt_delta_zero_mm<OP == WT_OP_MAX>(P, c, d, tid, nt);
-        else wt_delta_zero<QQ, TT>(P, c, d, tid, nt);
-#endif
-        WT_TICK(0);
-        WT_MARK(102);
-        int scale = 1;
-        if constexpr (MM) {
-            // one pass, no unit exponent: a float's order-preserving key needs none
-            for (int ch = 0; ch < nchunks; ch++) {
-                wt_delta_ranges_w1(P, c, d, ch * nt, tid, nt);
-                __syncthreads();
-                wt_delta_ranges_w2(P, c, d, tid, nt, 64u * U);
-                __syncthreads();
-                WT_TICK(1);
-                wt_delta_pass_mm<OP == WT_OP_MAX>(P, c, d, tid, nt);
-                __syncthreads();
-                WT_TICK(3);
-            }
-            if (tid == 0 && d.dsh->bad) wt_delta_mark_bad(P, c, k);     // a NaN or a -0.0: the general kernel's window
-        } else if (guess == 0) {
-            // no unit exponent known to this workgroup yet: exponent-range pass, then the delta pass
-            for (int ch = 0; ch < nchunks; ch++) {
-                wt_delta_ranges_w1(P, c, d, ch * nt, tid, nt);
-                __syncthreads();
-                wt_delta_ranges_w2(P, c, d, tid, nt, 64u * U);
-                __syncthreads();
-                WT_TICK(1);
-                wt_delta_pass1<U>(P, c, d, tid, nt);
-                __syncthreads();
-                WT_TICK(2);
-            }
-            const bool any = d.dsh->emin <= d.dsh->emax;
-            const bool ok = wt_delta_verdict(P, d, scale);
-            if (!ok && tid == 0) wt_delta_mark_bad(P, c, k);
-            for (int ch = 0; ch < nchunks; ch++) {
-                if (nchunks > 1) {
-                    wt_delta_ranges_w1(P, c, d, ch * nt, tid, nt);
-                    __syncthreads();
-                    wt_delta_ranges_w2(P, c, d, tid, nt, 64u * U);
-                    __syncthreads();
-                }
-                wt_delta_pass2<QQ, DF, TT, U>(P, c, d, scale, ok, false, true, tid, nt, ntr(ch), ch * nt);
-                __syncthreads();
-                WT_TICK(3);
-            }
-            if (any && ok) guess = scale;
-        } else {
-            // speculative single pass with the workgroup's unit (wt_delta_window_verdict)
-            for (int ch = 0; ch < nchunks; ch++) {
-                wt_delta_ranges_w1(P, c, d, ch * nt, tid, nt);
-                __syncthreads();
-                wt_delta_ranges_w2(P, c, d, tid, nt, 64u * U);
-                __syncthreads();
-                WT_TICK(1);
-                wt_delta_pass2<QQ, DF, TT, U>(P, c, d, guess, true, true, true, tid, nt, ntr(ch), ch * nt);
-                __syncthreads();
-                WT_TICK(3);
-            }
-            int lo;
-            bool ok;
-            scale = guess;
-            if (!wt_delta_window_verdict(P, d, guess, lo, ok)) {      // workgroup-uniform
-              if (!ok) {
-                // not provably exact whatever the unit: the patch kernel rewrites this window's values, and everything
-                // else about it -- breakpoints, coverage, run count -- is in place after the speculative pass.  (It used
-                // to be redone like the windows below: twice the time of a window, during which every later window sat
-                // in its look-back; 5 % such windows cost the kernel a third more time, round 4.)
-                if (tid == 0) wt_delta_mark_bad(P, c, k);
-              } else {
-                __syncthreads();            // every lane has read the verdict fields
-                wt_delta_rezero<QQ, TT>(P, c, d, tid, nt);
-                __syncthreads();
-                for (int ch = 0; ch < nchunks; ch++) {
-                    if (nchunks > 1) {
-                        wt_delta_ranges_w1(P, c, d, ch * nt, tid, nt);
-                        __syncthreads();
-                        wt_delta_ranges_w2(P, c, d, tid, nt, 64u * U);
-                        __syncthreads();
-                    }
-                    wt_delta_pass2<QQ, DF, TT, U>(P, c, d, lo, ok, false, false, tid, nt, ntr(ch), ch * nt);
-                    __syncthreads();
-                }
-                scale = lo;
-                guess = lo;
-              }
-            }
-        }
-        WT_MARK(105);
-        if constexpr (TT) {
-            // the scans split by set over 2 nts lanes, then one lane per position (wt_delta.h: phases A - C)
-            if (tid < 2 * nts) wt_delta_scan_w1_tt(P, c, d, DL2, tid, nts);
-            __syncthreads();
-            WT_MARK(107);
-            if (tid < 2 * nts) wt_delta_scan3_tt(P, c, d, DL2, scale, tid, nts);
-            __syncthreads();
-            wt_delta_combine_tt(P, c, d, tid, nt);
-            __syncthreads();
-            // a position whose variance cancels too much for the exact sums (wt_delta_scan3_tt): the window's values are the general kernel's
-            if (tid == 0 && d.dsh->risk && c.sh->bad_slot < 0) wt_delta_mark_bad(P, c, k);
-        } else if constexpr (MM) {
-            int32_t wc_mm = 0;
-            wt_delta_scan_w1_mm(P, c, d, wc_mm, tid, nt);
-            __syncthreads();
-            WT_MARK(107);
-            wt_delta_scan3_mm<OP == WT_OP_MAX>(P, c, d, wc_mm, L, tid, nt);
-            __syncthreads();
-        } else if constexpr (EP) {
-            // Sum / Mean: the bytes of the breakpoint / emitted bitmaps first ...
-            wt_delta_scan_w1<QQ>(P, c, d, DL, tid, nts);
-            __syncthreads();
-            WT_MARK(107);
-            ep_rank = wt_delta_scan3_cov(P, c, d, DL, ep_em, tid, nts);
-            __syncthreads();
-        } else {
-            if (WT_SCAN_LANE) wt_delta_scan_w1<QQ>(P, c, d, DL, tid, nts);
-            __syncthreads();
-            WT_MARK(107);
-            if (WT_SCAN_LANE) wt_delta_scan3<OP>(P, c, d, DL, L, scale, tid, nts);
-            __syncthreads();
-        }
-        WT_TICK(4);
-        WT_MARK(108);
-        // wave 0: run-count scan and look-back back to back (it owns the counts); the last lanes
-        // build the breakpoint jump table meanwhile
-        unsigned long long mine = 0;
-        if constexpr (EP) {
-            // the wavefronts' run counts are in epfx[0 .. nwaves): this one's first rank, and -- wave 0 -- the window's count, published at once
-            const int lane_ = tid & 63;
-            if (tid < 64) {
-                mine = wt_waves_before32(c.epfx, 0, nt >> 6, lane_);
-                WT_TICK(5);
-                if (tid == 0) wt_lookback_publish(P, c, k, mine);
-            }
-            ep_rank += wt_waves_before32(c.epfx, 0, tid >> 6, lane_);
-            // ... the count is out; now the values (wt_delta_scan3_val: nobody waits for them but this window's own staging)
-            wt_delta_scan3_val<OP>(P, c, d, DL, L, scale, tid, nts);
-        } else if (tid < 64) {
-            mine = wt_delta_escan_wave(P, c, tid);
-            WT_TICK(5);
-            if (tid == 0) wt_lookback_publish(P, c, k, mine);
-        }
-        wt_delta_nextw(P, c, tid, nt);
-        __syncthreads();
-        WT_MARK(110);
-        // the look-back's round trips to the status words overlap the staging of the other waves
-        // (and the predecessors get that much longer to publish)
-        if (tid < 64) {
-            wt_lookback_complete(P, c, k, tid, mine);
-            if constexpr (!EP) wt_delta_note_offset(P, c, tid);     // (lane 0 set the offset in the look-back: same wave, LDS in order)
-        }
-        WT_TICK(6);
-        if constexpr (TT) {
-            // two-sample launches: the Student tail of every emitted position is what the look-back of wave 0 overlaps -- the other
-            // wavefronts share the window's positions.  Two barriers before the staging: the first, because a scan lane's 8 results
-            // were written by other wavefronts' lanes (wt_delta_tail_tt); the second, because the staging reuses what the results
-            // lie in -- with the spare entries of WT_STAGE_AT, run number 1986 and later of a 2048-bp window are staged at
-            // acc[W ..], the results of the window's first positions, which their own lanes must have loaded by then
-            if (tid >= 64) wt_delta_tail_tt(P, d, tid - 64, nt - 64);
-            __syncthreads();
-            WT_TICK(2);             // (profile builds: the tail, less the look-back, in the slot of the exponent-range pass)
-            if (tid < nts) wt_delta_load_res_tt(P, d, L, tid);
-            __syncthreads();
-        }
-        if constexpr (EP) wt_delta_stage_ep<OP>(P, c, d, L, ep_em, DL.evmask, ep_rank, tid, nts);
-        else if (WT_SCAN_LANE) wt_delta_stage<OP>(P, c, d, L, tid, nts);
-        __syncthreads();
-        if constexpr (EP) { if (tid < 64) wt_delta_note_offset_ep(P, c, tid); }
-#ifdef WT_PROFILE_TAIL
-        WT_TICK(2);                 // (experiment: the tail of a window apart -- staging here, copy-out in "write", ticket + header in "zero")
-#endif
-        wt_delta_copy_out(P, c, d, tid, nt);
-        __syncthreads();
-#ifdef WT_PROFILE_TAIL
-        WT_TICK(7);
-#endif
-        WT_MARK(111);
-        if (tid == 0) {
-            wt_window_stats(P, c);
-            const long long kn = (long long) wt_glb_add64(&P.counters[WT_CTR_TICKET], 1ull);
-            c.sh->ticket = kn;
-            if (kn < P.n_windows) wt_phase_header(P, c, kn);
-        }
-#if WT_DELTA_ZERO_EARLY
-        if constexpr (MM) wt_delta_zero_mm<OP == WT_OP_MAX>(P, c, d, tid, nt);
-        else wt_delta_zero<QQ, TT>(P, c, d, tid, nt);
-#endif
-        __syncthreads();
-#ifdef WT_PROFILE_TAIL
-        WT_TICK(0);
-#else
-        WT_TICK(7);
-#endif
-    }
-#ifdef WT_PROFILE
-    if (tid == 0)
-        for (int q = 0; q < 8; q++) wt_glb_add64(&P.counters[WT_CTR_PROF + q], prof[q]);
-#endif
-}
-
-#undef WT_SCAN_LANE
-
-// Patch kernel: the general bitmap multiplexer over just the windows the difference-array kernel
-// could not prove exact (a NaN, an Inf, too wide a dynamic range).  That kernel has already emitted
-// those windows' runs -- coordinates, run count, position in the output -- so this one only has
-// to recompute their values in the reference's own summation order and store them at the recorded
-// offsets: no ticket, no look-back, no statistics.  One difference-array window (8192 bp) is
-// `ratio` general windows; the difference-array kernel recorded the run offset of 16 sub-ranges of
-// every such window, so every (window, sub-window) pair is a work item of its own.
-struct WtPatchArgs {
-    const int32_t *bad_list;            // difference-array window ids (slot order)
-    const long long *bad_goff;          // first run of each
-    const unsigned long long *n_bad;    // how many (device counter of the difference-array launch)
-    const int32_t *d_win_chrom;         // the difference-array launch's window tables
-    const int64_t *d_c_first_win;
-    int ratio;                          // its window width / this launch's
-};
-
-__device__ __forceinline__ long long wt_lane_lower_bound(const int32_t *fin, long long lo, long long hi, long long g, long long b);
-
-// The narrow-window index rows the patch kernel is going to read, and only those: for every window the
-// difference-array kernel recorded, the ratio + 1 boundaries inside it, per track, by binary search.  (Round 3 built the
-// WHOLE index at the patch kernel's window width whenever a launch had a window to patch -- 4 x the rows of the
-// 8192-bp index, a third of a millisecond per chromosome for a few hundred windows.)
-__global__ void __launch_bounds__(256) wt_patch_index_kernel(const WtParams P, const WtPatchArgs Q) {
-    const long long n_bad = (long long) *Q.n_bad;
-    const int N = P.n_tracks, R1 = Q.ratio + 1;
-    const long long total = n_bad * R1 * N;
-    for (long long t = (long long) blockIdx.x * 256 + threadIdx.x; t < total; t += (long long) gridDim.x * 256) {
-        const long long j = t / ((long long) R1 * N);
-        const int rem = (int) (t - j * R1 * N), r = rem / N, i = rem - r * N;
-        const long long kd = Q.bad_list[j];
-        const int ch = Q.d_win_chrom[kd];
-        const long long m = (kd - Q.d_c_first_win[ch]) * Q.ratio + r;
-        if (m > P.c_nwin[ch]) continue;             // (row c_nwin is the chromosome's last boundary)
-        const long long seg = (long long) ch * N + i;
-        const long long s0 = P.seg_off[seg], n = P.seg_off[seg + 1] - s0;
-        const long long b = (long long) P.cbase[ch] + (m << P.logW);
-        P.widx[(P.c_first_win[ch] + ch + m) * N + i] = (uint32_t) wt_lane_lower_bound(P.finish + s0, 0, n, n >> 1, b);
-    }
-}
-
-template <int OP, int K, bool MULTI>
-__global__ void __launch_bounds__(WT_MAX_BLOCK, WT_MIN_WAVES(K)) wt_patch_kernel(const WtParams P, const WtPatchArgs Q) {
-    typedef float ValT;
-    typedef float ScrT;
-    extern __shared__ __attribute__((aligned(16))) char wt_lds[];
-    WtCtx c;
-    wt_ctx_init(c, P, wt_lds);
-    WtLane<K> L;
-    const int tid = threadIdx.x, nt = blockDim.x;
-    const long long n_bad = (long long) *Q.n_bad;
-    const int N = P.n_tracks, NC = MULTI ? P.chunk_tracks : N, n_chunks = MULTI ? P.n_chunks : 1;
-    // work items = (window the difference-array kernel recorded, narrower window h inside it): independent of one
-    // another -- the recording kernel left the run offset of every sub-range (wt_delta_note_offset)
-    const long long n_items = n_bad * Q.ratio;
-    for (long long item = blockIdx.x; item < n_items; item += gridDim.x) {
-        const long long j = item / Q.ratio;
-        const int h = (int) (item - j * Q.ratio);
-        const long long kd = Q.bad_list[j];
-        const int ch = Q.d_win_chrom[kd];
-        const long long m = kd - Q.d_c_first_win[ch];
-        const long long goff = Q.bad_goff[j * WT_BAD_SUB + h * (WT_BAD_SUB / Q.ratio)];
-        {
-            const long long mg = m * Q.ratio + h;
-            if (mg >= P.c_nwin[ch]) continue;               // workgroup-uniform
-            const long long k = P.c_first_win[ch] + mg;
-            __syncthreads();                                // the previous window is done with the shared block
-            if (tid == 0) wt_phase_header(P, c, k);
-            wt_phase_zero(P, c, true, tid, nt);
-            __syncthreads();
-            // same sweeps as wt_reduce_kernel (chunked tracks: the first evaluation pass rides on the
-            // sweep that builds the bitmaps; var / stddev / CV take a second one)
-            constexpr int npass = wt_eval_passes(OP);
-            WtAcc<K> A;
-            wt_eval_init<OP, K>(A);
-            for (int cc = 0; cc < n_chunks; cc++) {
-                const int t_lo = cc * NC, t_hi = (t_lo + NC < N) ? t_lo + NC : N;
-                if (MULTI && cc > 0) {
-                    wt_phase_zero(P, c, false, tid, nt);
-                    __syncthreads();
-                }
-                wt_phase_load<ValT>(P, c, t_lo, t_hi, false, tid, nt);
-                __syncthreads();
-                wt_phase_count_a(P, c, t_lo, t_hi, tid, nt);
-                __syncthreads();
-                wt_phase_count_b(P, c, t_lo, t_hi, tid, nt);
-                __syncthreads();
-                if (MULTI) {
-                    wt_phase_eval_chunk<OP, ValT, ScrT, K>(P, c, A, 0, t_lo, t_hi, true, tid, nt);
-                    __syncthreads();
-                }
-            }
-            if (MULTI && npass == 2) wt_eval_mid<OP, K>(P, A);
-            wt_phase_emask(P, c, OP == WT_OP_TTEST, tid, nt);
-            __syncthreads();
-            wt_phase_escan(P, c, tid, nt);
-            __syncthreads();
-            const long long n_emit = (long long) c.epfx[P.n_words];
-            if (tid == 0) { c.sh->n_emit = (int32_t) n_emit; c.sh->goffset = goff; }
-#pragma unroll
-            for (int pass = MULTI ? 1 : 0; pass < npass; pass++) {
-                for (int cc = 0; cc < n_chunks; cc++) {
-                    const int t_lo = cc * NC, t_hi = (t_lo + NC < N) ? t_lo + NC : N;
-                    if (MULTI) {
-                        wt_phase_zero(P, c, false, tid, nt);
-                        __syncthreads();
-                        wt_phase_load<ValT>(P, c, t_lo, t_hi, false, tid, nt);
-                        __syncthreads();
-                        wt_phase_count_a(P, c, t_lo, t_hi, tid, nt);
-                        __syncthreads();
-                        wt_phase_count_b(P, c, t_lo, t_hi, tid, nt);
-                        __syncthreads();
-                    }
-                    wt_phase_eval_chunk<OP, ValT, ScrT, K>(P, c, A, pass, t_lo, t_hi, false, tid, nt);
-                    if (MULTI) __syncthreads();
-                }
-                if (pass == 0 && npass == 2) wt_eval_mid<OP, K>(P, A);
-            }
-            wt_phase_eval_finish<OP, ValT, ScrT, K>(P, c, A, L, tid, nt);
-            __syncthreads();
-            wt_phase_write<OP, ValT, K>(P, c, L, tid, nt);
-        }
-    }
-}
-
 // Each block owns ONE contiguous span of intervals: a single binary search finds the
 // (chrom,track) segment of its first interval, every lane then walks its cursor forward.  The
 // finish[] reads of the next sub-chunk are in flight while the current one is applied.
@@ -696,33 +133,6 @@ __device__ __forceinline__ int wt_index_row_chrom(const WtParams &P, long long r
     for (int hi = P.n_chrom; hi - lo > 1;) {
         const int mid = (lo + hi) >> 1;
         if (P.c_first_win[mid] + mid <= row) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// first x in [lo, hi) with fin[x] >= b (hi if none), starting from a guess g in [lo, hi)
-__device__ __forceinline__ long long wt_lane_lower_bound(const int32_t *fin, long long lo, long long hi, long long g, long long b) {
-    if (lo >= hi) return lo;
-    if ((long long) fin[g] >= b) {
-        hi = g;
-        for (long long d = 1;; d <<= 1) {
-            const long long q = hi - d;
-            if (q < lo) break;
-            if ((long long) fin[q] < b) { lo = q + 1; break; }
-            hi = q;
-        }
-    } else {
-        lo = g + 1;
-        for (long long d = 1;; d <<= 1) {
-            const long long q = lo + d - 1;
-            if (q >= hi) break;
-            if ((long long) fin[q] >= b) { hi = q; break; }
-            lo = q + 1;
-        }
-    }
-    while (lo < hi) {
-        const long long mid = (lo + hi) >> 1;
-        if ((long long) fin[mid] < b) lo = mid + 1; else hi = mid;
     }
     return lo;
 }
@@ -1523,117 +933,6 @@ int wtamd_trackset_index(wtamd_trackset *ts, int op, void *stream) {
     return wt_build_index(ts, w, plan, (hipStream_t) stream);
 }
 
-}  // extern "C"
-
-// Launch functor for wt_dispatch
-struct WtLaunch {
-    WtParams P;
-    int T = 0, lds = 0, grid = 0;
-    bool small_tiles = false;           // difference-array Sum / Mean: the pass in 128-run tiles (wt_launch_delta)
-    hipStream_t stream = nullptr;
-    int num_cu = 256;
-    char **gscratch = nullptr;
-    size_t *gscratch_bytes = nullptr;
-    hipError_t err = hipSuccess;
-
-    template <int OP, class ValT, class ScrT, int K, bool MULTI, int NR = 0>
-    void run() {
-        auto kern = wt_reduce_kernel<OP, ValT, ScrT, K, MULTI, NR>;
-        if (lds > 48 * 1024) {
-            err = hipFuncSetAttribute((const void *) kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            if (err != hipSuccess) return;
-        }
-        int per_cu = 0;
-        err = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, T, (size_t) lds);
-        if (err != hipSuccess) return;
-        if (per_cu < 1) per_cu = 1;
-        long long g = (long long) num_cu * per_cu;
-        if (g > P.n_windows) g = P.n_windows;
-        if (g < 1) g = 1;
-        if (P.g_scratch_slab || P.g_attr_slab) {    // one global slab per resident workgroup
-            if (P.g_scratch_slab && g > 2ll * num_cu) g = 2ll * num_cu;
-            const size_t need = (size_t) g * (size_t) (P.g_scratch_slab + P.g_attr_slab);
-            if (*gscratch_bytes < need) {
-                (void) hipFree(*gscratch);      // synchronises with earlier launches
-                *gscratch = nullptr; *gscratch_bytes = 0;
-                err = hipMalloc((void **) gscratch, need);
-                if (err != hipSuccess) return;
-                *gscratch_bytes = need;
-            }
-            P.g_scratch = *gscratch;
-        }
-        grid = (int) g;
-        hipLaunchKernelGGL(kern, dim3((unsigned) grid), dim3((unsigned) T), (size_t) lds, stream, P);
-        err = hipGetLastError();
-    }
-};
-
-template <int OP, int K, bool MULTI>
-static hipError_t wt_launch_patch_t(const WtParams &P, const WtPatchArgs &Q, int T, int lds, int num_cu, long long n_bad,
-                                    hipStream_t s) {
-    auto kern = wt_patch_kernel<OP, K, MULTI>;
-    hipError_t e = hipSuccess;
-    if (lds > 48 * 1024) {
-        e = hipFuncSetAttribute((const void *) kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return e;
-    }
-    int per_cu = 0;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, T, (size_t) lds);
-    if (e != hipSuccess) return e;
-    if (per_cu < 1) per_cu = 1;
-    long long g = (long long) num_cu * per_cu;
-    if (g > n_bad * Q.ratio) g = n_bad * Q.ratio;
-    if (g < 1) g = 1;
-    hipLaunchKernelGGL(kern, dim3((unsigned) g), dim3((unsigned) T), (size_t) lds, s, P, Q);
-    return hipGetLastError();
-}
-
-// csrc/wt_walk.hip (its own translation unit: the three instantiations of the kernel take minutes to compile)
-hipError_t wt_walk_launch(WtParams &P, int nr, int T, int lds, int num_cu, char **gscratch, size_t *gscratch_bytes, hipStream_t s, int *grid);
-
-template <int OP, bool DF = false>
-static void wt_launch_delta(WtLaunch &L) {
-    // 128-run tiles when a window holds fewer than 8 of the 256-run ones per wavefront (round 6: the last round of tiles
-    // leaves wavefronts idle -- mean run 64: 50 tiles over 16 wavefronts, -6.5 % with the small ones; mean run 200 -2.5 %; mean run 16,
-    // 12.5 per wavefront: +1 %, so the large ones stay there).  WTAMD_DELTA_U=2 / 4 forces one.
-    // (the t-test's 2048-bp windows: 50 tiles over 12 wavefronts, -6 % with the small ones; the variance family measured +-0 at mean run 16
-    //  and +2.5 % at 200 with them and keeps the large ones; Max / Min have a pass of their own, wt_delta_pass_mm)
-    constexpr bool TWO = OP == WT_OP_SUM || OP == WT_OP_MEAN || OP == WT_OP_TTEST;
-    auto kern = (TWO && L.small_tiles) ? wt_delta_kernel<OP, DF, TWO ? 2 : WT_DELTA_U> : wt_delta_kernel<OP, DF, WT_DELTA_U>;
-    // (the attribute and the occupancy query once per instantiation, device and launch shape: they are host calls of 50-150 us each,
-    //  and they sat between the event that starts the reduction's clock and the launch -- round 6: the bench's events read 0.12-0.28 ms
-    //  more per launch than rocprofv3's kernel durations)
-    static std::mutex mu;
-    static std::map<std::tuple<int, int, int>, int> known;
-    int dev = 0;
-    (void) hipGetDevice(&dev);
-    int per_cu = 0;
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        auto it = known.find(std::make_tuple(dev, L.T + (L.small_tiles ? 1 : 0), L.lds));
-        if (it != known.end()) per_cu = it->second;
-    }
-    if (per_cu == 0) {
-        if (L.lds > 48 * 1024) {
-            L.err = hipFuncSetAttribute((const void *) kern, hipFuncAttributeMaxDynamicSharedMemorySize, L.lds);
-            if (L.err != hipSuccess) return;
-        }
-        L.err = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, L.T, (size_t) L.lds);
-        if (L.err != hipSuccess) return;
-        if (per_cu < 1) per_cu = 1;
-        std::lock_guard<std::mutex> lk(mu);
-        known[std::make_tuple(dev, L.T + (L.small_tiles ? 1 : 0), L.lds)] = per_cu;
-    }
-    long long g = (long long) L.num_cu * per_cu;
-    if (g > L.P.n_windows) g = L.P.n_windows;
-    if (g < 1) g = 1;
-    L.grid = (int) g;
-    hipLaunchKernelGGL(kern, dim3((unsigned) L.grid), dim3((unsigned) L.T), (size_t) L.lds, L.stream, L.P);
-    L.err = hipGetLastError();
-}
-
-extern "C" {
-
 static int wt_check_desc(const wtamd_trackset *ts, const wtamd_reduce_desc *d) {
     if (!ts || !d) return wt_fail(WTAMD_ERR_ARG, "NULL argument");
     if (d->op < 0 || d->op >= WTAMD_OP_COUNT_) return wt_fail(WTAMD_ERR_ARG, "unknown op");
@@ -1668,50 +967,23 @@ static int wt_launch_patch(wtamd_trackset *ts, int delta_W, int op, uint32_t fla
     if (rc != WTAMD_OK) return rc;
     rc = wt_get_windows(ts, plan.W, &w, s);
     if (rc != WTAMD_OK) return rc;
-    WtParams P;
+    WtLaunch L;
+    WtParams &P = L.P;
     wt_fill_params(ts, w, plan, P);
     P.op = op; P.flags = flags; P.n_set0 = op == WT_OP_TTEST ? n_set0 : 0;
     P.capacity = runs->capacity;
     P.o_start = runs->start; P.o_finish = runs->finish; P.o_value = runs->value;
     P.chrom_run_off = runs->chrom_run_off ? runs->chrom_run_off : ts->d_chrom_run_off;
+    L.T = plan.T; L.lds = plan.lds_bytes; L.stream = s; L.num_cu = ts->num_cu;
     WtPatchArgs Q;
     Q.bad_list = dw->d_bad_list; Q.bad_goff = dw->d_bad_goff;
     Q.n_bad = ts->d_counters + WT_CTR_DELTA_BAD;
     Q.d_win_chrom = dw->d_win_chrom; Q.d_c_first_win = dw->d_cfirst;
     Q.ratio = delta_W / plan.W;
-    if (!w->indexed) {
-        // no index at this window width yet: only the rows of the recorded windows are filled in (w->indexed stays false)
-        long long blocks = (n_bad * (Q.ratio + 1) * ts->n_tracks + 255) / 256;
-        if (blocks > 4ll * ts->num_cu) blocks = 4ll * ts->num_cu;
-        if (blocks < 1) blocks = 1;
-        hipLaunchKernelGGL(wt_patch_index_kernel, dim3((unsigned) blocks), dim3(256), 0, s, P, Q);
-        WT_HIP(hipGetLastError());
-    }
-    const bool multi = plan.n_chunks > 1;
-    hipError_t e;
-#define WT_PATCH_GO(OPC, KK, MM) e = wt_launch_patch_t<OPC, KK, MM>(P, Q, plan.T, plan.lds_bytes, ts->num_cu, n_bad, s)
-    if (op == WT_OP_SUM) {
-        if (plan.ppt == 4) { if (multi) WT_PATCH_GO(WT_OP_SUM, 4, true); else WT_PATCH_GO(WT_OP_SUM, 4, false); }
-        else { if (multi) WT_PATCH_GO(WT_OP_SUM, 1, true); else WT_PATCH_GO(WT_OP_SUM, 1, false); }
-    } else if (op == WT_OP_MEAN) {
-        if (plan.ppt == 4) { if (multi) WT_PATCH_GO(WT_OP_MEAN, 4, true); else WT_PATCH_GO(WT_OP_MEAN, 4, false); }
-        else { if (multi) WT_PATCH_GO(WT_OP_MEAN, 1, true); else WT_PATCH_GO(WT_OP_MEAN, 1, false); }
-    } else if (op == WT_OP_MAX || op == WT_OP_MIN) {
-        if (plan.ppt != 4) return wt_fail(WTAMD_ERR_INTERNAL, "no general plan compatible with the difference-array windows");
-        if (op == WT_OP_MAX) { if (multi) WT_PATCH_GO(WT_OP_MAX, 4, true); else WT_PATCH_GO(WT_OP_MAX, 4, false); }
-        else { if (multi) WT_PATCH_GO(WT_OP_MIN, 4, true); else WT_PATCH_GO(WT_OP_MIN, 4, false); }
-    } else if (op == WT_OP_TTEST) {
-        if (plan.ppt != 4) return wt_fail(WTAMD_ERR_INTERNAL, "no general plan compatible with the difference-array windows");
-        if (multi) WT_PATCH_GO(WT_OP_TTEST, 4, true); else WT_PATCH_GO(WT_OP_TTEST, 4, false);
-    } else {
-        // var / stddev / entropy / CV: 4 positions per lane only (what the plans pick unless forced)
-        if (plan.ppt != 4) return wt_fail(WTAMD_ERR_INTERNAL, "no general plan compatible with the difference-array windows");
-        if (op == WT_OP_VAR) { if (multi) WT_PATCH_GO(WT_OP_VAR, 4, true); else WT_PATCH_GO(WT_OP_VAR, 4, false); }
-        else if (op == WT_OP_CV) { if (multi) WT_PATCH_GO(WT_OP_CV, 4, true); else WT_PATCH_GO(WT_OP_CV, 4, false); }
-        else { if (multi) WT_PATCH_GO(WT_OP_STDDEV, 4, true); else WT_PATCH_GO(WT_OP_STDDEV, 4, false); }
-    }
-#undef WT_PATCH_GO
-    if (e != hipSuccess) return wt_fail(WTAMD_ERR_HIP, std::string("patch kernel launch: ") + hipGetErrorString(e));
+    // (no index at this window width yet: only the rows of the recorded windows are filled in, w->indexed stays false)
+    if (!wt_patch_launch(L, Q, op, plan.ppt, plan.n_chunks > 1, n_bad, !w->indexed))
+        return wt_fail(WTAMD_ERR_INTERNAL, "no general plan compatible with the difference-array windows");
+    if (L.err != hipSuccess) return wt_fail(WTAMD_ERR_HIP, std::string("patch kernel launch: ") + hipGetErrorString(L.err));
     WT_HIP(hipEventRecord(ts->ev_r1, s));       // the reduction's time includes its patches
     ts->stats.patched_windows = (int32_t) n_bad;
     return WTAMD_OK;
@@ -1725,7 +997,7 @@ static int wt_reduce_impl(wtamd_trackset *ts, int op, uint32_t flags, int n_set0
     std::string err;
     // Sum / Mean: exact difference-array kernel first.  It verifies every window.  A few windows
     // it cannot prove exact (NaN, Inf, too wide a dynamic range) keep their coordinates and get
-    // their values from the general kernel restricted to them (wt_patch_kernel); if they are many
+    // their values from the general kernel restricted to them (the patch kernel); if they are many
     // the whole launch is redone by the general kernel and this data stays on it.  The verdict
     // depends on the data and the windows only (not on the op or its flags), so it is established
     // once per track set -- that first launch is waited for even when the caller asked for an
@@ -1766,7 +1038,7 @@ static int wt_reduce_impl(wtamd_trackset *ts, int op, uint32_t flags, int n_set0
 
 static int wt_reduce_plan(wtamd_trackset *ts, const WtPlan &plan, int op, uint32_t flags, int n_set0, wtamd_runs *runs,
                           double *d_tile, uint8_t *d_inplay, int64_t *n_runs, hipStream_t s) {
-    if (plan.T > (plan.delta ? ((wt_op_is_var_family(op) || op == WT_OP_TTEST) ? WT_DELTA_SQ_BLOCK : WT_DELTA_BLOCK) : WT_MAX_BLOCK)) return wt_fail(WTAMD_ERR_ARG, "workgroup size above the kernel's launch bound");
+    if (plan.T > (plan.delta ? ((wt_op_is_var_family(op) || op == WT_OP_TTEST) ? wt_delta_sq_block : wt_delta_block) : wt_reduce_max_block)) return wt_fail(WTAMD_ERR_ARG, "workgroup size above the kernel's launch bound");
     WtWindows *w = nullptr;
     int rc = wt_get_windows(ts, plan.W, &w, s);
     if (rc != WTAMD_OK) return rc;
@@ -1826,19 +1098,10 @@ static int wt_reduce_plan(wtamd_trackset *ts, const WtPlan &plan, int op, uint32
         }
         WT_HIP(hipEventRecord(ts->ev_r0, s));
         if (plan.delta) {
-            switch (op) {
-            case WT_OP_SUM: if (L.P.delta_df) wt_launch_delta<WT_OP_SUM, true>(L); else wt_launch_delta<WT_OP_SUM>(L); break;
-            case WT_OP_MEAN: if (L.P.delta_df) wt_launch_delta<WT_OP_MEAN, true>(L); else wt_launch_delta<WT_OP_MEAN>(L); break;
-            case WT_OP_VAR: wt_launch_delta<WT_OP_VAR>(L); break;
-            case WT_OP_CV: wt_launch_delta<WT_OP_CV>(L); break;
-            case WT_OP_TTEST: wt_launch_delta<WT_OP_TTEST>(L); break;
-            case WT_OP_MAX: wt_launch_delta<WT_OP_MAX>(L); break;
-            case WT_OP_MIN: wt_launch_delta<WT_OP_MIN>(L); break;
-            default: wt_launch_delta<WT_OP_STDDEV>(L); break;      // stddev, entropy (reducers.c:665)
-            }
+            wt_delta_launch(L, op);
         } else if (plan.walk_S) {
             L.err = wt_walk_launch(L.P, plan.regcol, L.T, L.lds, L.num_cu, L.gscratch, L.gscratch_bytes, L.stream, &L.grid);
-        } else if (!wt_dispatch(op, ts->value_f64, ts->scratch_f32, plan.ppt, plan.n_chunks > 1 || plan.scratch_slab > 0, L, plan.regcol)) {
+        } else if (!wt_reduce_launch(L, op, ts->value_f64, ts->scratch_f32, plan.ppt, plan.n_chunks > 1 || plan.scratch_slab > 0, plan.regcol)) {
             return wt_fail(WTAMD_ERR_ARG, "op not dispatchable");
         }
         if (L.err != hipSuccess) return wt_fail(WTAMD_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(L.err));
@@ -1902,12 +1165,9 @@ static int wt_reduce_plan(wtamd_trackset *ts, const WtPlan &plan, int op, uint32
                 fprintf(stderr, " %s %.1f%%", names[q], tot ? 100.0 * ts->h_counters[WT_CTR_PROF + q] / tot : 0.0);
             fprintf(stderr, " (total %.3g cycles over all workgroups)\n", (double) tot);
             unsigned long long p2[8] = {0};
-            if (hipMemcpyFromSymbol(p2, HIP_SYMBOL(wt_prof2), sizeof p2) == hipSuccess && (p2[0] | p2[4])) {
+            if (wt_prof2_take(p2))
                 fprintf(stderr, "[wt_profile] register column, cycles summed over waves: gather %.3g  sort/park %.3g  count loop %.3g  erf %.3g  median sort+select %.3g\n",
                         (double) p2[0], (double) p2[1], (double) p2[2], (double) p2[3], (double) p2[4]);
-                unsigned long long z[8] = {0};
-                (void) hipMemcpyToSymbol(HIP_SYMBOL(wt_prof2), z, sizeof z);
-            }
         }
 #endif
         if (ts->h_counters[WT_CTR_ERROR] & WT_ERR_LOOKBACK) return wt_fail(WTAMD_ERR_INTERNAL, "look-back timed out");

@@ -1,4 +1,4 @@
-// wt_plan.h -- host-side planning shared by the HIP engine (wt_engine.hip) and
+// wt_plan.h -- host-side planning shared by the HIP engine (wt_engine.hip, the kernel units) and
 // the CPU emulator used by the no-GPU tests: window width / workgroup size /
 // LDS carve for a given track count and reducer, and the per-chromosome window
 // tables.  Pure C++, no HIP.
@@ -9,6 +9,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -531,42 +532,33 @@ static inline void wt_dispatch_types2(bool value_f64, bool scratch_f32, bool mul
     }
 }
 
+// One op: the register-column forms of Median / MWU (regcol = slots per lane), or the op by value / scratch type and
+// positions per lane.  Callable on its own: a kernel unit instantiates only the ops it asks for.
 template <int OP, class F>
-static inline void wt_dispatch_types(bool value_f64, bool scratch_f32, int ppt, bool multi, F &f) {
+static inline void wt_dispatch_op(bool value_f64, bool scratch_f32, int ppt, bool multi, F &f, int regcol = 0) {
+    if constexpr (OP == WT_OP_MEDIAN || OP == WT_OP_MWU) {
+        if (regcol && !value_f64 && scratch_f32 && !multi) {
+            if (regcol == 32) f.template run<OP, float, float, 2, false, 32>();
+            else if (regcol == 64) f.template run<OP, float, float, 2, false, 64>();
+            else f.template run<OP, float, float, 2, false, 128>();
+            return;
+        }
+    }
     if (wt_op_needs_scratch(OP) || ppt == 1) wt_dispatch_types2<OP, 1>(value_f64, scratch_f32, multi, f);
     else wt_dispatch_types2<OP, 4>(value_f64, scratch_f32, multi, f);
 }
 
+// The switch over the ops OPS: false if `op` is none of them
+template <int... OPS, class F>
+static inline bool wt_dispatch_ops(int op, bool value_f64, bool scratch_f32, int ppt, bool multi, F &f, int regcol = 0) {
+    if (op == WT_OP_ENTROPY) op = WT_OP_STDDEV;     // reference reducers.c:665: entropy runs the stddev pop
+    return ((op == OPS ? (wt_dispatch_op<OPS>(value_f64, scratch_f32, ppt, multi, f, regcol), true) : false) || ...);
+}
+
 template <class F>
 static inline bool wt_dispatch(int op, bool value_f64, bool scratch_f32, int ppt, bool multi, F &f, int regcol = 0) {
-    if (regcol && (op == WT_OP_MEDIAN || op == WT_OP_MWU) && !value_f64 && scratch_f32 && !multi) {
-        if (op == WT_OP_MEDIAN) {
-            if (regcol == 32) f.template run<WT_OP_MEDIAN, float, float, 2, false, 32>();
-            else if (regcol == 64) f.template run<WT_OP_MEDIAN, float, float, 2, false, 64>();
-            else f.template run<WT_OP_MEDIAN, float, float, 2, false, 128>();
-        } else {
-            if (regcol == 32) f.template run<WT_OP_MWU, float, float, 2, false, 32>();
-            else if (regcol == 64) f.template run<WT_OP_MWU, float, float, 2, false, 64>();
-            else f.template run<WT_OP_MWU, float, float, 2, false, 128>();
-        }
-        return true;
-    }
-    switch (op) {
-    case WT_OP_SUM: wt_dispatch_types<WT_OP_SUM>(value_f64, scratch_f32, ppt, multi, f); return true;
-    case WT_OP_PRODUCT: wt_dispatch_types<WT_OP_PRODUCT>(value_f64, scratch_f32, ppt, multi, f); return true;
-    case WT_OP_MEAN: wt_dispatch_types<WT_OP_MEAN>(value_f64, scratch_f32, ppt, multi, f); return true;
-    case WT_OP_VAR: wt_dispatch_types<WT_OP_VAR>(value_f64, scratch_f32, ppt, multi, f); return true;
-    case WT_OP_STDDEV: case WT_OP_ENTROPY:   // reference reducers.c:665: entropy runs the stddev pop
-        wt_dispatch_types<WT_OP_STDDEV>(value_f64, scratch_f32, ppt, multi, f); return true;
-    case WT_OP_CV: wt_dispatch_types<WT_OP_CV>(value_f64, scratch_f32, ppt, multi, f); return true;
-    case WT_OP_MIN: wt_dispatch_types<WT_OP_MIN>(value_f64, scratch_f32, ppt, multi, f); return true;
-    case WT_OP_MAX: wt_dispatch_types<WT_OP_MAX>(value_f64, scratch_f32, ppt, multi, f); return true;
-    case WT_OP_MEDIAN: wt_dispatch_types<WT_OP_MEDIAN>(value_f64, scratch_f32, ppt, multi, f); return true;
-    case WT_OP_TTEST: wt_dispatch_types<WT_OP_TTEST>(value_f64, scratch_f32, ppt, multi, f); return true;
-    case WT_OP_MWU: wt_dispatch_types<WT_OP_MWU>(value_f64, scratch_f32, ppt, multi, f); return true;
-    case WT_OP_MULTIPLEX: wt_dispatch_types<WT_OP_MULTIPLEX>(value_f64, scratch_f32, ppt, multi, f); return true;
-    default: return false;
-    }
+    return wt_dispatch_ops<WT_OP_SUM, WT_OP_PRODUCT, WT_OP_MEAN, WT_OP_VAR, WT_OP_STDDEV, WT_OP_CV, WT_OP_MIN, WT_OP_MAX, WT_OP_MEDIAN, WT_OP_TTEST, WT_OP_MWU,
+                           WT_OP_MULTIPLEX>(op, value_f64, scratch_f32, ppt, multi, f, regcol);
 }
 
 // True iff every default survives a round trip through float (then float

@@ -1,10 +1,12 @@
-// wt_walk.hip -- gfx950 kernel of MedianReduction by walking (logic in wt_walk.h) and its launcher, a translation unit of
-// its own next to wt_engine.hip.  Compiled only by hipcc --offload-arch=gfx950.
+// wt_walk.hip -- gfx950 kernels of MedianReduction / MWUReduction by walking (logic in wt_walk.h, wt_mwalk.h) and their launcher
+// (wt_kernels.h), one of the kernel units next to wt_engine.hip.  Compiled only by hipcc --offload-arch=gfx950.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 
 #include "../../include/wiggletools_amd.h"
 #include "wt_core.h"
+#include "wt_kernels.h"
+#include "wt_launch.h"
 
 #define WT_MARK(x) do { } while (0)
 #ifdef WT_PROFILE
@@ -214,30 +216,17 @@ __global__ void __launch_bounds__(MAXT, 1) wt_mwalk_kernel(const WtParams P) {
     }
 }
 
-// (nr: the register-column slots the bitmap kernel would use for this track count -- eligibility only)
 hipError_t wt_walk_launch(WtParams &P, int nr, int T, int lds, int num_cu, char **gscratch, size_t *gscratch_bytes, hipStream_t s, int *grid) {
     (void) nr;
     auto kern = P.walk_mwu ? wt_mwalk_kernel<256> : (P.walk_pair ? (T > 256 ? wt_walk_kernel<512, true> : wt_walk_kernel<256, true>) : wt_walk_kernel<256, false>);
-    hipError_t e = hipSuccess;
-    if (lds > 48 * 1024) {
-        e = hipFuncSetAttribute((const void *) kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return e;
-    }
     int per_cu = 0;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, T, (size_t) lds);
+    hipError_t e = wt_blocks_per_cu((const void *) kern, T, lds, &per_cu);
     if (e != hipSuccess) return e;
-    if (per_cu < 1) per_cu = 1;
     long long g = (long long) num_cu * per_cu;
     if (g > P.n_windows) g = P.n_windows;
     if (g < 1) g = 1;
-    const size_t need = (size_t) g * (size_t) P.g_scratch_slab;        // one slab of events per resident workgroup
-    if (*gscratch_bytes < need) {
-        (void) hipFree(*gscratch);          // synchronises with earlier launches
-        *gscratch = nullptr; *gscratch_bytes = 0;
-        e = hipMalloc((void **) gscratch, need);
-        if (e != hipSuccess) return e;
-        *gscratch_bytes = need;
-    }
+    e = wt_reserve_slab(gscratch, gscratch_bytes, (size_t) g * (size_t) P.g_scratch_slab);     // one slab of events per resident workgroup
+    if (e != hipSuccess) return e;
     P.g_scratch = *gscratch;
     *grid = (int) g;
     hipLaunchKernelGGL(kern, dim3((unsigned) g), dim3((unsigned) T), (size_t) lds, s, P);
