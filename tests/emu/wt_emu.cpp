@@ -725,14 +725,11 @@ long long wtemu_reduce(int n_chrom, int n_tracks, const int64_t *seg_off, const 
         std::string err;
         if (delta) wt_make_delta_plan_for(R.plan, n_tracks, op);
         else {
-            // the engine's wt_pick_plan: the median over float tracks walks
-            bool walk = false;
-            if (op == WT_OP_MEDIAN && !value_is_f64 && !o_tile && !getenv("WTAMD_NO_WALK"))
-                if (const int nr = wt_regcol_slots(n_tracks, op, s32, n_set0)) walk = wt_make_walk_plan(R.plan, n_tracks, nr, 0.0);
-            // ... and so does MWU when asked to (wt_mwalk.h; WTAMD_MWALK=1: the engine's switch)
-            if (op == WT_OP_MWU && !value_is_f64 && !o_tile && getenv("WTAMD_MWALK") && atoi(getenv("WTAMD_MWALK")) != 0 && !getenv("WTAMD_NO_WALK"))
-                if (const int nr = wt_regcol_slots(n_tracks, op, s32, n_set0)) walk = wt_make_walk_plan(R.plan, n_tracks, nr, 0.0, 160 * 1024, n_set0);
-            if (!walk && !wt_make_plan(n_tracks, op, s32, R.plan, err, 80 * 1024, 160 * 1024, n_set0)) { fprintf(stderr, "wtemu: %s\n", err.c_str()); return -10; }
+            // the engine's general plan (wt_plan.h), with the emulator's own switches: the median walks unless WTAMD_NO_WALK, MWU
+            // (wt_mwalk.h) when WTAMD_MWALK=1 asks for it -- the engine's sample of the values is not taken here
+            const bool walk = !o_tile && !getenv("WTAMD_NO_WALK");
+            const bool mwu_walk = walk && getenv("WTAMD_MWALK") && atoi(getenv("WTAMD_MWALK")) != 0;
+            if (!wt_pick_general_plan(n_tracks, op, value_is_f64 != 0, s32, n_set0, walk, mwu_walk, 0.0, R.plan, err)) { fprintf(stderr, "wtemu: %s\n", err.c_str()); return -10; }
         }
         WtWindowTables tab;
         wt_make_windows(n_chrom, n_tracks, seg_off, fs.data(), lf.data(), R.plan.W, tab, range_lo, range_hi);
@@ -759,8 +756,8 @@ long long wtemu_reduce(int n_chrom, int n_tracks, const int64_t *seg_off, const 
         if (delta) { P.bad_list = bad_list.data(); P.bad_goff = bad_goff.data(); wt_delta_defaults_params(defaults, n_tracks, P); }
         // few inexact windows: the general kernel rewrites the values of just those (the engine's
         // wt_patch_kernel); many: it redoes everything
-        const bool patching = !delta && attempt == 1 && delta_bad > 0 && delta_bad * 4 <= (long long) delta_tab.n_windows &&
-                              delta_W >= R.plan.W && delta_W % R.plan.W == 0 && delta_W / R.plan.W <= WT_BAD_SUB;
+        const bool patching = !delta && attempt == 1 && delta_bad > 0 && wt_few_enough_to_patch(delta_bad, delta_tab.n_windows) &&
+                              wt_patch_compatible(R.plan, delta_W, s32, value_is_f64 != 0);
         if (patching) {
             const int ratio = delta_W / R.plan.W;
             R.patch = true;

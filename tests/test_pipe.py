@@ -55,24 +55,48 @@ def test_pipe_two_sample_and_tile(oracle, lib):
     assert np.array_equal(got[3], exp[4].sum(axis=1))       # the run's inplay_count (multiplexer.h:27)
 
 
-def test_pipe_difference_array_with_patched_windows(oracle, lib, monkeypatch):
-    """Float tracks, zero defaults: the exact difference-array kernel runs; NaN / Inf / a wide
-    dynamic range in a few windows make it hand those windows to the patch kernel, which the pipe
-    launches once the batch's counters are back -- before the runs are shipped."""
-    from wiggletools_amd.pipe import stream_runlists
+def _tracks_with_inexact_windows():
+    """Six float tracks over 240 000 bp with NaN, Inf and 2^-120 next to 2^100 in four runs: the difference-array kernel
+    cannot prove those windows exact (8192-bp windows: a batch needs > 4 per inexact one to be patched rather than redone)."""
     from wiggletools_amd.runlists import synth
-    monkeypatch.setenv("WTAMD_DELTA_MIN_TRACKS", "1")
-    t = synth(6, [240000], mean_run=9, seed=3, dtype=np.float32)        # (8192-bp windows: a batch needs > 4 per inexact one)
+    t = synth(6, [240000], mean_run=9, seed=3, dtype=np.float32)
     v = t.value
     v[100] = np.nan
     v[len(v) // 2] = np.inf
     v[len(v) // 3] = 2.0 ** -120
     v[len(v) // 3 + 1] = 2.0 ** 100
+    return t
+
+
+def test_pipe_difference_array_with_patched_windows(oracle, lib, monkeypatch):
+    """Float tracks, zero defaults: the exact difference-array kernel runs; NaN / Inf / a wide
+    dynamic range in a few windows make it hand those windows to the patch kernel, which the pipe
+    launches once the batch's counters are back -- before the runs are shipped."""
+    from wiggletools_amd.pipe import stream_runlists
+    monkeypatch.setenv("WTAMD_DELTA_MIN_TRACKS", "1")
+    t = _tracks_with_inexact_windows()
     d = t.as_dict()
     for op in ("sum", "mean"):
         got, st = stream_runlists(t, op, 80000, depth=2, lib=lib)
         assert_runs_equal(got, oracle.reduce(d, op), 0.0, op)
         assert st["delta_batches"] == st["batches"] > 1
+
+
+def test_pipe_patched_windows_compressed(oracle, lib, monkeypatch):
+    """The same batches with WTAMD_PIPE_COMPRESS: the compression of a batch ran before its counters came back, on runs
+    whose inexact windows still held the difference-array kernel's values -- when the batch is collected the pipe patches
+    those windows and then compresses and ships AGAIN.  A consumer applying the reference's wrapper to what arrives gets
+    what it gets on the oracle's runs; every batch stayed on the difference-array kernel; fewer runs travelled."""
+    from wiggletools_amd.pipe import stream_runlists
+    monkeypatch.setenv("WTAMD_DELTA_MIN_TRACKS", "1")
+    t = _tracks_with_inexact_windows()
+    d = t.as_dict()
+    for op in ("sum", "mean"):
+        plain = oracle.reduce(d, op)
+        got, st = stream_runlists(t, op, 80000, depth=2, lib=lib, compress=True)
+        assert_runs_equal(oracle.compress(*got), oracle.compress(*plain), 0.0, op)
+        assert st["delta_batches"] == st["batches"] > 1
+        assert len(got[0]) < len(plain[0])
 
 
 def test_pipe_device_side_compression(oracle, lib):

@@ -1,4 +1,4 @@
-"""The process-wide pools behind the pipes (csrc/wt_pipe.h: page-locked staging and device buffers): a second reducer of the
+"""The process-wide pools behind the pipes (csrc/wt_pool.h: page-locked staging and device buffers): a second reducer of the
 same shape in one process must not page-lock or map anything again, and must give the same runs."""
 import ctypes as C
 

@@ -1,5 +1,5 @@
 """The stand-alone passes around the reducers -- csrc/wt_moments.hip, csrc/wt_compress.hip, csrc/wt_map.hip and
-wt_auc_kernel / wt_pearson_kernel of csrc/wt_engine.hip -- at every seam of their launch geometry, against references that
+wt_auc_kernel / wt_pearson_kernel of csrc/wt_moments.hip -- at every seam of their launch geometry, against references that
 are exact (tests/exact.py) or pinned on the compiled reference (oracle.compress, oracle.map_values).
 
 These are plain .hip translation units the CPU emulator never compiles: a GPU test is their only guard, and the older ones run

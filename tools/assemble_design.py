@@ -107,7 +107,7 @@ add(body(13, "#### Operator chains inside the pipeline (`wt_map_chain_async`, `w
 add("")
 add("### 4.9 Pipeline kernels and the BigWig kernels")
 add("")
-add(body(11, "#### `wt_gather_kernel`, `wt_export_kernel` (`csrc/wt_pipe.h`)"))
+add(body(11, "#### `wt_gather_kernel`, `wt_export_kernel` (`csrc/wt_pipe.hip`)"))
 add("")
 add(body(28, "#### BigWig sections decoded on the device (`csrc/wt_inflate.h`, `csrc/wt_bwdev_core.h`, `csrc/wt_bwdev.hip`)"))
 add("")
@@ -119,7 +119,7 @@ add(body(14, "### 4.10 Roofline accounting (bound: HBM)"))
 add("")
 add(new("05_measurement"))
 add("")
-add("## 6. The streaming pipeline and the files (north-star N1; `csrc/wt_pipe.h`, `csrc/wt_iter_abi.cpp` + `csrc/wt_abi_*.h`)")
+add("## 6. The streaming pipeline and the files (north-star N1; `csrc/wt_pipe.h` + `csrc/wt_pipe.hip`, `csrc/wt_iter_abi.cpp` + `csrc/wt_abi_*.h`)")
 add("")
 add(body(21))
 add("")

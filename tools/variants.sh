@@ -1,4 +1,4 @@
-# compares kernel variants (csrc/build.py build_source_variant over KERNEL_SRCS + wt_engine.hip) on the same box: C2 whole genome, kernel ms
+# compares kernel variants (csrc/build.py build_source_variant over KERNEL_SRCS + wt_engine.hip, the units that read -DWT_PROFILE; wt_pipe.hip does not) on the same box: C2 whole genome, kernel ms
 # usage: tools/variants.sh <name> ...   ("-" = the default library)
 for v in "$@"; do
   L=$PWD/wiggletools_amd/csrc/libwiggletools_amd.so

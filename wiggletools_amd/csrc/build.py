@@ -7,7 +7,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SO = os.path.join(HERE, "libwiggletools_amd.so")
 # the kernel units (wt_kernels.h): the heavy compiles, one thread each
 KERNEL_SRCS = ["wt_reduce_stream.hip", "wt_reduce_moments.hip", "wt_reduce_order.hip", "wt_patch_kernels.hip", "wt_delta_kernels.hip", "wt_walk.hip"]
-SRCS = KERNEL_SRCS + ["wt_engine.hip", "wt_compress.hip", "wt_moments.hip", "wt_map.hip", "wt_synth.hip", "wt_bwdev.hip", "wt_defaults.cpp", "wt_iter_abi.cpp", "wt_bigwig.cpp", "wt_bwwrite.cpp"]
+SRCS = KERNEL_SRCS + ["wt_engine.hip", "wt_pipe.hip", "wt_compress.hip", "wt_moments.hip", "wt_map.hip", "wt_synth.hip", "wt_bwdev.hip", "wt_defaults.cpp", "wt_iter_abi.cpp", "wt_bigwig.cpp", "wt_bwwrite.cpp"]
 LIBS = ["-lz"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
          "-Wall", "-Wno-unused-function", "-Wno-pass-failed"]
@@ -17,7 +17,8 @@ def build_source_variant(srcs, name, extra_flags):
     """Experiment helper: recompiles the given sources (one name or a list; SRCS: all) with extra flags, in parallel, and links
     them with the objects of the last build() (run build() first) into libwiggletools_amd_<name>.so (select it at run time with
     WTAMD_LIB=<path>), e.g. build_source_variant("wt_bwdev.hip", "round8", ["-DWT_INF_ROUND=8"]) or, for a switch of the reducing
-    kernels, build_source_variant(KERNEL_SRCS + ["wt_engine.hip"], "prof", ["-DWT_PROFILE"])."""
+    kernels, build_source_variant(KERNEL_SRCS + ["wt_engine.hip"], "prof", ["-DWT_PROFILE"]): the six kernel units and the engine,
+    which prints their counters, are the units a -DWT_PROFILE variant needs; wt_pipe.hip and the side units do not read the switch."""
     from concurrent.futures import ThreadPoolExecutor
     srcs = [srcs] if isinstance(srcs, str) else list(srcs)
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

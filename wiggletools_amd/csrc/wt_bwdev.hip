@@ -29,11 +29,9 @@
 #include <cstring>
 #include <string>
 
-#include "../../include/wiggletools_amd.h"
+#include "wt_host.h"
 #include "wt_inflate.h"
 #include "wt_bwdev_core.h"
-
-int wt_fail_ext(int code, const std::string &msg);     // wt_engine.hip
 
 namespace {
 
@@ -337,34 +335,29 @@ int wt_bw_decode_async(const void *h_bytes, void *d_bytes, long long n_bytes, co
                        float *o_value, int64_t *d_seg_off, unsigned long long *h_status, int copy_blocks, hipStream_t s_copy,
                        hipEvent_t e_copied, hipStream_t s_dec) {
     if (n_sec < 0 || n_sec > 0x7FFFFFFFll - 64 || plain_stride <= 0 || (plain_stride & 15) || plain_stride > 0x7FFFFFFFll)
-        return wt_fail_ext(WTAMD_ERR_ARG, "wt_bw_decode_async: bad section count / stride");
+        return wt_fail(WTAMD_ERR_ARG, "wt_bw_decode_async: bad section count / stride");
     const long long n = n_sec > 0 ? n_sec : 1;
     uint8_t *plain = (uint8_t *) scratch;
     int32_t *plain_len = (int32_t *) (plain + n * plain_stride);
     uint32_t *counts = (uint32_t *) (plain_len + n);
     long long *offsets = (long long *) (((uintptr_t) (counts + n) + 7) & ~(uintptr_t) 7);
     uint32_t *err = (uint32_t *) (offsets + n + 1);
-#define WT_BW_HIP(expr)                                                                                  \
-    do {                                                                                                 \
-        hipError_t e_ = (expr);                                                                          \
-        if (e_ != hipSuccess) return wt_fail_ext(WTAMD_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
     const long long n16 = (n_bytes + 15) / 16;
     // the copy engine by default (one contiguous range: no per-range cost), WTAMD_BW_COPY=kernel: the copy kernel
     static const bool sdma = !(getenv("WTAMD_BW_COPY") && !strcmp(getenv("WTAMD_BW_COPY"), "kernel"));
     if (n16 > 0 && sdma) {
         // the copy engine instead of a kernel: nothing of the transfer runs on the CUs the inflate kernel occupies
-        WT_BW_HIP(hipMemcpyAsync(d_bytes, h_bytes, (size_t) n16 * 16, hipMemcpyHostToDevice, s_copy));
+        WT_HIP(hipMemcpyAsync(d_bytes, h_bytes, (size_t) n16 * 16, hipMemcpyHostToDevice, s_copy));
     } else if (n16 > 0) {
         long long grid = copy_blocks > 0 ? copy_blocks : 64;
         const long long need = (n16 + 1023) / 1024;
         if (grid > need) grid = need;
         hipLaunchKernelGGL(wt_bw_copy_kernel, dim3((unsigned) grid), dim3(256), 0, s_copy, (const wt_u32x4 *) h_bytes, (wt_u32x4 *) d_bytes, n16);
-        WT_BW_HIP(hipGetLastError());
+        WT_HIP(hipGetLastError());
     }
-    WT_BW_HIP(hipEventRecord(e_copied, s_copy));
-    WT_BW_HIP(hipStreamWaitEvent(s_dec, e_copied, 0));
-    WT_BW_HIP(hipMemsetAsync(err, 0, sizeof(uint32_t), s_dec));
+    WT_HIP(hipEventRecord(e_copied, s_copy));
+    WT_HIP(hipStreamWaitEvent(s_dec, e_copied, 0));
+    WT_HIP(hipMemsetAsync(err, 0, sizeof(uint32_t), s_dec));
     const WtBwSection *secs = (const WtBwSection *) d_secs;
     const WtBwTrack *tracks = (const WtBwTrack *) d_tracks;
     if (n_sec > 0) {
@@ -375,19 +368,18 @@ int wt_bw_decode_async(const void *h_bytes, void *d_bytes, long long n_bytes, co
         else
             hipLaunchKernelGGL(wt_bw_inflate_kernel<8>, dim3(g), dim3(WT_BW_INF_LANES), 0, s_dec, secs, tracks, (int) n_sec,
                                (const uint8_t *) d_comp, plain, (uint32_t) plain_stride, plain_len, counts);
-        WT_BW_HIP(hipGetLastError());
+        WT_HIP(hipGetLastError());
         hipLaunchKernelGGL(wt_bw_count_kernel, dim3((unsigned) n_sec), dim3(64), 0, s_dec, secs, tracks, (int) n_sec, (const uint8_t *) d_comp, plain,
                            (uint32_t) plain_stride, plain_len, counts, err);
-        WT_BW_HIP(hipGetLastError());
+        WT_HIP(hipGetLastError());
     }
     hipLaunchKernelGGL(wt_bw_scan_kernel, dim3(1), dim3(1024), 0, s_dec, tracks, n_tracks, (int) n_sec, counts, offsets, d_seg_off,
                        capacity, err, h_status);
-    WT_BW_HIP(hipGetLastError());
+    WT_HIP(hipGetLastError());
     if (n_sec > 0) {
         hipLaunchKernelGGL(wt_bw_scatter_kernel, dim3((unsigned) n_sec), dim3(64), 0, s_dec, secs, tracks, (int) n_sec, plain,
                            (uint32_t) plain_stride, plain_len, offsets, capacity, err, o_start, o_finish, o_value);
-        WT_BW_HIP(hipGetLastError());
+        WT_HIP(hipGetLastError());
     }
-#undef WT_BW_HIP
     return WTAMD_OK;
 }

@@ -25,7 +25,7 @@
 #include <cstdio>
 #include <string>
 
-#include "../../include/wiggletools_amd.h"
+#include "wt_host.h"
 
 namespace {
 
@@ -221,8 +221,6 @@ __global__ void wc_chrom_offsets(const int64_t *chrom_run_off, int n_chrom, long
 
 }  // namespace
 
-extern "C" const char *wtamd_last_error(void);
-
 namespace {
 thread_local std::string g_err;
 }
@@ -283,7 +281,7 @@ extern "C" int wtamd_runs_compress(const wtamd_runs *in, int64_t n_runs, int32_t
 }
 
 
-// ---- in-stream flavour for the pipeline (wt_pipe.h): one chromosome, the run count still on the
+// ---- in-stream flavour for the pipeline (wt_pipe.hip): one chromosome, the run count still on the
 // device (*d_n, at most `capacity`), scratch provided by the caller (WC scratch words: see
 // wt_compress_scratch_words), nothing waits.  *d_n_out receives the number of merged runs.
 long long wt_compress_scratch_words(long long capacity) {

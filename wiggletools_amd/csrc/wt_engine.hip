@@ -1,34 +1,30 @@
 // wt_engine.hip -- the bulk C ABI (wtamd_*) of include/wiggletools_amd.h: planner glue, launches, the patch / probe state
-// machine, the small kernels below and -- included at the end -- the pipeline (wt_pipe.h).  The reducing kernels live in units
-// of their own behind wt_kernels.h.  Compiled only by hipcc --offload-arch=gfx950.
+// machine and the small kernels below.  Its internal interface is wt_trackset.h: the streaming pipeline (wt_pipe.hip) is a
+// unit of its own built on it.  The reducing kernels live in units of their own behind wt_kernels.h, the integrators
+// (AUC, Pearson, run moments) in wt_moments.hip.  Compiled only by hipcc --offload-arch=gfx950.
 //
 // Kernels
 //   wt_index_kernel     window index (widx): contiguous span of input runs per block, 4 per lane
 //   wt_index_coarse_kernel / wt_index_search_kernel   the same index by search
 //   wt_extents_kernel   first start / last finish per (chrom, track) segment
 //   wt_validate_kernel  input contract (sorted, non-overlapping, positive length)
-//   wt_auc_kernel       sum (finish-start)*value (+ span) over a run list (AUC, meanI)
-//   wt_pearson_kernel   Pearson of two tracks over their Multiplexer tile
 #include <hip/hip_runtime.h>
 
-#include <chrono>
 #include <cstdio>
 #include <thread>
 #include <atomic>
-#include <sys/mman.h>
-#include <unistd.h>
 #include <cstring>
 #include <map>
 #include <mutex>
 #include <string>
 #include <vector>
 
-#include "../../include/wiggletools_amd.h"
+#include "wt_host.h"
+#include "wt_trackset.h"
 #include "wt_core.h"
 #include "wt_plan.h"
 #include "wt_kernels.h"
 #include "wt_devscope.h"
-#include "wt_bwdev_core.h"
 
 // ---------------------------------------------------------------------------
 // kernels
@@ -205,137 +201,6 @@ __global__ void __launch_bounds__(256) wt_extents_kernel(const int64_t *seg_off,
     last_finish[s] = hi > lo ? finish[hi - 1] : 0;
 }
 
-// AUC: statistics.c:103-120.  Deterministic two-level sum.
-__global__ void __launch_bounds__(256) wt_auc_kernel(const int32_t *start, const int32_t *finish, const double *value,
-                                                      long long n, double *partial, double *partial_span,
-                                                      const unsigned long long *n_dev = nullptr) {
-    __shared__ double red[256];
-    double acc = 0, span = 0;
-    if (n_dev && (long long) *n_dev < n) n = (long long) *n_dev;       // (pipeline: the run count only exists on the device)
-    const long long stride = (long long) gridDim.x * blockDim.x;
-    for (long long r = (long long) blockIdx.x * blockDim.x + threadIdx.x; r < n; r += stride) {
-        const double v = value[r];
-        if (v == v) {                                   // NaN runs are skipped (statistics.c:78, 110)
-            const double len = (double) (finish[r] - start[r]);
-            acc += len * v;
-            span += len;
-        }
-    }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int) threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
-    if (partial_span) {                                 // MeanIntegrator also needs the non-NaN span
-        __syncthreads();
-        red[threadIdx.x] = span;
-        __syncthreads();
-        for (int s = 128; s > 0; s >>= 1) {
-            if ((int) threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) partial_span[blockIdx.x] = red[0];
-    }
-}
-
-__global__ void wt_auc_final_kernel(const double *partial, int n, double *out) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        double acc = 0;
-        for (int i = 0; i < n; i++) acc += partial[i];
-        *out = acc;
-    }
-}
-
-// ---------------------------------------------------------------------------
-// Pearson correlation of two tracks over the Multiplexer tile (reference PearsonIntegrator,
-// statistics.c:414-465).  The reference updates {count, sum, T_XX, T_XY, T_YY} run by run with the
-// weighted Welford / Chan step (its `new_mean` is old sum / new count; expanding
-// n*L/(n+L) * (X - mean)^2 gives exactly its expression).  Here every lane applies that step IN ITS
-// UNEXPANDED FORM, n*L/(n+L) * (X - mean)^2, to a contiguous slice of runs, and slices are merged
-// pairwise in genome order with the same formula for two aggregates -- mathematically identical.
-// The expanded form sums terms of size mean^2 to get one of size deviation^2; in the reference's one long
-// pass that costs (mean/deviation)^2 of the digits with errors of either sign, but at the start of
-// every slice -- 65 536 of them, n / (n + L) far from 1 -- the errors are biased: on a track of
-// relative variance 1e-10 (70 001 runs) T_XX came out 2.1e-8 off where the reference's own pass is
-// 4.9e-10 off; unexpanded it is 2.9e-13 off (tests/test_side_kernels.py::test_gpu_pearson_constant_track_rule,
-// against exact rational arithmetic; the other tests hold 1e-9 against the oracle).
-// ---------------------------------------------------------------------------
-struct WtMoments {
-    double n, sx, sy, txx, txy, tyy;
-};
-
-__device__ inline void wt_moments_add_run(WtMoments &m, double X, double Y, double L) {
-    if (m.n > 0) {
-        const double dx = X - m.sx / m.n, dy = Y - m.sy / m.n;
-        const double w = m.n * L / (m.n + L);
-        m.txx += dx * dx * w;
-        m.txy += dx * dy * w;
-        m.tyy += dy * dy * w;
-    }
-    m.n += L;
-    m.sx += X * L;
-    m.sy += Y * L;
-}
-
-// a := a (+) b, b following a in genome order
-__device__ inline void wt_moments_merge(WtMoments &a, const WtMoments &b) {
-    if (b.n == 0) return;
-    if (a.n == 0) { a = b; return; }
-    const double n = a.n + b.n;
-    const double dx = b.sx / b.n - a.sx / a.n, dy = b.sy / b.n - a.sy / a.n;
-    const double w = a.n * b.n / n;
-    a.txx += b.txx + dx * dx * w;
-    a.txy += b.txy + dx * dy * w;
-    a.tyy += b.tyy + dy * dy * w;
-    a.n = n;
-    a.sx += b.sx;
-    a.sy += b.sy;
-}
-
-__global__ void __launch_bounds__(256) wt_pearson_kernel(const int32_t *start, const int32_t *finish, const double *tile,
-                                                          const uint8_t *inplay, double dx, double dy, long long n,
-                                                          WtMoments *partial, const unsigned long long *n_dev = nullptr) {
-    __shared__ WtMoments red[256];
-    if (n_dev && (long long) *n_dev < n) n = (long long) *n_dev;
-    const long long total_lanes = (long long) gridDim.x * blockDim.x;
-    const long long per = (n + total_lanes - 1) / total_lanes;          // contiguous slice per lane
-    const long long lane_id = (long long) blockIdx.x * blockDim.x + threadIdx.x;
-    long long lo = lane_id * per, hi = lo + per;
-    if (hi > n) hi = n;
-    WtMoments m = {0, 0, 0, 0, 0, 0};
-    for (long long r = lo; r < hi; r++) {
-        const double X = inplay[2 * r] ? tile[2 * r] : dx;
-        const double Y = inplay[2 * r + 1] ? tile[2 * r + 1] : dy;
-        wt_moments_add_run(m, X, Y, (double) (finish[r] - start[r]));
-    }
-    red[threadIdx.x] = m;
-    __syncthreads();
-    for (int s = 1; s < 256; s <<= 1) {                                 // ordered pairwise merge
-        if ((threadIdx.x & (2 * s - 1)) == 0) wt_moments_merge(red[threadIdx.x], red[threadIdx.x + s]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
-}
-
-__global__ void wt_pearson_final_kernel(const WtMoments *partial, int n, double *out) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        WtMoments m = {0, 0, 0, 0, 0, 0};
-        for (int i = 0; i < n; i++) wt_moments_merge(m, partial[i]);
-        double txx = m.txx, tyy = m.tyy;                               // (constant track: see wtamd_pearson_finish)
-        if (m.n > 0) {
-            const double mx = m.sx / m.n, my = m.sy / m.n;
-            if (txx <= m.n * mx * mx * 1e-14) txx = 0;
-            if (tyy <= m.n * my * my * 1e-14) tyy = 0;
-        }
-        const double den = txx * tyy;
-        out[0] = den ? m.txy / sqrt(den) : __builtin_nan("");          // statistics.c:421-423
-        out[1] = m.n; out[2] = m.sx; out[3] = m.sy; out[4] = m.txx; out[5] = m.txy; out[6] = m.tyy;
-    }
-}
-
-
 // Input contract check (sorted, non-overlapping, positive-length runs inside every (chrom, track)
 // segment -- anything else is undefined behaviour in the reference's Multiplexer too,
 // multiplexer.c:76-96, and bedReader.c:46-49 checks it for text input).  One lane per run.
@@ -363,81 +228,10 @@ __global__ void __launch_bounds__(256) wt_validate_kernel(const int32_t *start, 
 // ---------------------------------------------------------------------------
 static thread_local std::string g_last_error;
 
-static int wt_fail(int code, const std::string &msg) {
+int wt_fail(int code, const std::string &msg) {
     g_last_error = msg;
     return code;
 }
-int wt_fail_ext(int code, const std::string &msg) { return wt_fail(code, msg); }   // for the other translation units
-
-#define WT_HIP(expr)                                                                           \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess)                                                                  \
-            return wt_fail(WTAMD_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));  \
-    } while (0)
-
-struct WtWindows {
-    WtPlan plan_geom;        // only W matters for the tables
-    WtWindowTables tab;
-    int32_t *d_cbase = nullptr, *d_cnwin = nullptr, *d_chi = nullptr, *d_win_chrom = nullptr;
-    int64_t *d_cfirst = nullptr;
-    uint32_t *d_widx = nullptr;
-    uint32_t *d_cidx = nullptr;         // coarse index of the searched window index (every 64th row)
-    unsigned long long *d_status = nullptr;
-    int32_t *d_bad_list = nullptr;      // difference-array launches: windows not provably exact ...
-    long long *d_bad_goff = nullptr;    // ... and where their runs start (both [n_windows])
-    bool indexed = false;
-    // capacities of the device tables (entries); the tables are reused and only ever grow
-    int64_t cap_chrom = 0, cap_win = 0, cap_widx = 0, cap_bad = 0, cap_cidx = 0;
-    bool tab_valid = false;             // tab / device tables describe the track set's current data
-    int64_t *h_tab = nullptr;           // pinned staging of the per-chromosome tables (pipeline slots: asynchronous upload)
-    // round 6: cbase | cnwin | chi | cfirst | win_chrom live in ONE allocation (d_tabs) and travel in ONE copy -- a NEW track set's first
-    // index paid five hipMallocs and five blocking copies for them, 0.1 ms of host time per chromosome of a resident pass
-    char *d_tabs = nullptr;
-    int64_t cap_tabs = 0;               // bytes
-};
-
-struct wtamd_trackset {
-    int n_chrom = 0, n_tracks = 0;
-    bool value_f64 = false;
-    bool owns = false;
-    int64_t n_intervals = 0;
-    std::vector<int64_t> seg_off;
-    std::vector<double> defaults;
-    std::vector<int32_t> first_start, last_finish;
-    std::vector<int32_t> range_lo, range_hi;     // optional run-start ranges (empty = none)
-    int32_t *d_start = nullptr, *d_finish = nullptr;
-    void *d_value = nullptr;
-    int64_t *d_seg_off = nullptr;
-    double *d_defaults = nullptr;
-    unsigned long long *d_counters = nullptr;
-    unsigned long long *h_counters = nullptr;   // pinned
-    unsigned long long *h_debug = nullptr;      // pinned, device-visible (debug builds)
-    int64_t *d_chrom_run_off = nullptr;         // scratch when the caller passes none
-    char *d_gscratch = nullptr;                 // median / MWU columns of very many tracks (grown on demand)
-    size_t gscratch_bytes = 0;
-    double *d_mwu_table = nullptr;              // MWUReduction's last step as a table (wt_mwu_make_table), for set sizes mwu_n1 / mwu_n2
-    int mwu_n1 = -1, mwu_n2 = -1, mwu_kmax = 0;
-    int mwu_few_ties = -1;                      // MWUReduction's kernel by the data (wt_mwu_few_ties): -1 not looked at yet, 1 walk (wt_mwalk.h), 0 register columns
-    std::vector<double *> mwu_retired;          // tables of earlier set sizes (freed with the track set)
-    std::map<int, WtWindows> windows;           // keyed by W
-    hipEvent_t ev_i0 = nullptr, ev_i1 = nullptr, ev_r0 = nullptr, ev_r1 = nullptr;
-    bool have_index_time = false, have_reduce_time = false;
-    wtamd_stats stats{};
-    int device = 0;
-    int num_cu = 256;
-    bool scratch_f32 = false;
-    // Sum / Mean over float tracks: what a completed difference-array launch found out about this data
-    // the difference-array launches' verdict on this data, per class of reducer -- [0] Sum / Mean / the var family (exponent range
-    // of a window), [1] TTestReduction (its own, narrower windows, and positions whose variance cancels: wt_delta_scan3_tt)
-    // [2] Max / Min (only a NaN or a -0.0 sends a window to the general kernel)
-    bool delta_failed_[3] = {false, false, false};      // many windows are not provably exact: the class uses the general kernel
-    bool delta_verified_[3] = {false, false, false};    // verdict known: delta_n_bad windows (few) get patched by the general kernel
-    long long delta_n_bad_[3] = {0, 0, 0};
-    // pipeline slot (wt_pipe.h): the run lists are rebound per batch, device tables are reused,
-    // every upload is asynchronous on the launch stream from pinned staging
-    bool pipe_mode = false;
-};
 
 template <class T>
 static hipError_t wt_grow(T **p, int64_t *cap, int64_t need) {
@@ -459,6 +253,7 @@ static void wt_free_windows(WtWindows &w) {
     w = WtWindows();
 }
 
+// (the wtamd_* entries below and, among them, the wt_* functions of wt_trackset.h: those are marked extern "C++")
 extern "C" {
 
 const char *wtamd_last_error(void) { return g_last_error.c_str(); }
@@ -482,7 +277,7 @@ static std::mutex g_warm_mu;
 static std::thread *g_warm_thread = nullptr;
 static bool g_warm_started = false;
 
-static void wt_warmup_join() {
+extern "C++" void wt_warmup_join() {
     std::thread *t = nullptr;
     { std::lock_guard<std::mutex> lk(g_warm_mu); t = g_warm_thread; g_warm_thread = nullptr; }
     if (t) { t->join(); delete t; }
@@ -530,7 +325,7 @@ int wtamd_current_device(void) {
     return d;
 }
 
-static int wt_trackset_common(const wtamd_tracks *t, wtamd_trackset *ts) {
+extern "C++" int wt_trackset_common(const wtamd_tracks *t, wtamd_trackset *ts) {
     if (!t || t->n_chrom < 0 || t->n_tracks <= 0 || !t->seg_off || !t->defaults)
         return wt_fail(WTAMD_ERR_ARG, "wtamd_trackset_create: bad tracks descriptor");
     if (wtamd_device_count() <= 0) return wt_fail(WTAMD_ERR_NODEVICE, "no HIP device visible");
@@ -571,7 +366,7 @@ static int wt_trackset_common(const wtamd_tracks *t, wtamd_trackset *ts) {
 
 // The window arithmetic (w0 + W, look-ahead sentinels) is 32-bit: keep a margin below INT32_MAX.
 // Loud, at creation -- a run that close to 2^31 would otherwise be silently lost.
-static int wt_check_extents(wtamd_trackset *ts) {
+extern "C++" int wt_check_extents(wtamd_trackset *ts) {
     for (size_t q = 0; q < ts->last_finish.size(); q++)
         if (ts->seg_off[q + 1] > ts->seg_off[q] && ts->last_finish[q] > WTAMD_MAX_COORD) {
             const int64_t bad = ts->last_finish[q];
@@ -851,19 +646,8 @@ static bool wt_wants_delta(const wtamd_trackset *ts, int op) {
 // Events (run starts, plus a finish wherever a gap follows) per base pair the track set is expected to hold: the walking
 // kernel sizes its per-position slots from it.  Contiguous runs assumed for a quarter of them to be followed by a gap.
 static double wt_events_per_bp(const wtamd_trackset *ts) {
-    const int N = ts->n_tracks;
-    double span = 0;
-    for (int c = 0; c < ts->n_chrom; c++) {
-        int64_t lo = INT64_MAX, hi = INT64_MIN;
-        for (int i = 0; i < N; i++) {
-            const size_t s = (size_t) c * N + i;
-            if (s + 1 >= ts->seg_off.size() || ts->seg_off[s + 1] <= ts->seg_off[s] || s >= ts->first_start.size()) continue;
-            lo = std::min<int64_t>(lo, ts->first_start[s]);
-            hi = std::max<int64_t>(hi, ts->last_finish[s]);
-        }
-        if (hi > lo) span += (double) (hi - lo);
-    }
-    return span > 0 ? 1.25 * (double) ts->n_intervals / span : 0.0;
+    const int64_t span = wt_span(ts);
+    return span > 0 ? 1.25 * (double) ts->n_intervals / (double) span : 0.0;
 }
 
 // MWUReduction has two kernels, and which one is faster is a matter of the VALUES (round 6; chromosome 21, 50 v 50): the register
@@ -889,30 +673,47 @@ static bool wt_mwu_few_ties(wtamd_trackset *ts, hipStream_t stream) {
     return ts->mwu_few_ties != 0;
 }
 
-// The general (non difference-array) plan: MedianReduction over float tracks walks (wt_walk.h), everything else
-// -- and the median with WTAMD_NO_WALK=1, or when a Multiplexer tile is wanted -- takes the bitmap kernel.
+// The general (non difference-array) plan (wt_plan.h wt_pick_general_plan), with what the engine knows: the switches and the data.
+// MWUReduction by walking (wt_mwalk.h): when the values say so (wt_mwu_few_ties) -- on the generator's 800 levels it needs
+// 284 wave-wide VALU instructions per output run where the bitmap kernel's register columns need 253 (chromosome 21:
+// 43.9 against 35.6 ms; profiles/r05_mwu_walk_vs_bitmap.json).  WTAMD_NO_WALK=1: the bitmap kernel for both.
 static bool wt_pick_plan(wtamd_trackset *ts, int op, int n_set0, WtPlan &plan, std::string &err, hipStream_t stream = nullptr) {
-    if (op == WT_OP_MEDIAN && !ts->value_f64 && !getenv("WTAMD_NO_WALK"))
-        if (const int nr = wt_regcol_slots(ts->n_tracks, op, ts->scratch_f32, n_set0))
-            if (wt_make_walk_plan(plan, ts->n_tracks, nr, wt_events_per_bp(ts))) return true;
-    // MWUReduction by walking (wt_mwalk.h): when the values say so (wt_mwu_few_ties) -- on the generator's 800 levels it needs
-    // 284 wave-wide VALU instructions per output run where the bitmap kernel's register columns need 253 (chromosome 21:
-    // 43.9 against 35.6 ms; profiles/r05_mwu_walk_vs_bitmap.json)
-    // (same domain as the register columns, wt_regcol_slots: float tracks, float-exact defaults, at most 64 per set).
     static const int mwalk = getenv("WTAMD_MWALK") ? (atoi(getenv("WTAMD_MWALK")) != 0 ? 1 : 0) : -1;      // (-1: by the data)
-    if (op == WT_OP_MWU && mwalk != 0 && !ts->value_f64 && !getenv("WTAMD_NO_WALK") && (mwalk == 1 || wt_mwu_few_ties(ts, stream)))
-        if (const int nr = wt_regcol_slots(ts->n_tracks, op, ts->scratch_f32, n_set0))
-            if (wt_make_walk_plan(plan, ts->n_tracks, nr, wt_events_per_bp(ts), 160 * 1024, n_set0)) return true;
-    return wt_make_plan(ts->n_tracks, op, ts->scratch_f32, plan, err, 80 * 1024, 160 * 1024, n_set0);
+    const bool walk = !getenv("WTAMD_NO_WALK");
+    const bool mwu_walk = op == WT_OP_MWU && mwalk != 0 && !ts->value_f64 && walk && (mwalk == 1 || wt_mwu_few_ties(ts, stream));
+    const double events_per_bp = (op == WT_OP_MEDIAN || op == WT_OP_MWU) ? wt_events_per_bp(ts) : 0.0;
+    return wt_pick_general_plan(ts->n_tracks, op, ts->value_f64, ts->scratch_f32, n_set0, walk, mwu_walk, events_per_bp, plan, err);
+}
+
+// What was learnt about the track set's data is void: the difference-array launches verify again (delta_failed: they are
+// not to be tried at all) and every width's window index describes the old run lists.
+static void wt_trackset_forget(wtamd_trackset *ts, bool delta_failed) {
+    for (int q = 0; q < 3; q++) { ts->delta_verified_[q] = false; ts->delta_failed_[q] = delta_failed; ts->delta_n_bad_[q] = 0; }
+    for (auto &kv : ts->windows) kv.second.indexed = false;
+}
+
+extern "C++" int wt_trackset_rebind(wtamd_trackset *ts, int64_t n, const int64_t *seg_off, int32_t range_lo, int32_t range_hi, bool value_f64,
+                                    int32_t *d_start, int32_t *d_finish, void *d_value, bool delta_failed) {
+    ts->n_intervals = n;
+    ts->seg_off.assign(seg_off, seg_off + (int64_t) ts->n_chrom * ts->n_tracks + 1);
+    ts->range_lo[0] = range_lo;
+    ts->range_hi[0] = range_hi;
+    ts->value_f64 = value_f64;
+    ts->scratch_f32 = !ts->value_f64 && wt_defaults_fit_f32(ts->defaults.data(), ts->n_tracks);
+    ts->d_start = d_start; ts->d_finish = d_finish; ts->d_value = d_value;
+    // mwu_few_ties is KEPT: the sample of the pipe's first MWU batch decides for all its batches (ADVICE.md lists this as an
+    // open item; sampling per batch would put a stream synchronisation and a copy into every one).  wtamd_trackset_index clears it.
+    wt_trackset_forget(ts, delta_failed);
+    for (auto &kv : ts->windows) kv.second.tab_valid = false;       // other extents: every width's window tables are rebuilt
+    return wt_check_extents(ts);
 }
 
 int wtamd_trackset_index(wtamd_trackset *ts, int op, void *stream) {
     if (!ts) return wt_fail(WTAMD_ERR_ARG, "ts == NULL");
     // an explicit re-index means the run lists may have been rewritten in place (zero-copy track
     // sets): what was learnt about their values is void, the next Sum / Mean verifies again
-    for (int q = 0; q < 3; q++) { ts->delta_verified_[q] = false; ts->delta_failed_[q] = false; ts->delta_n_bad_[q] = 0; }
+    wt_trackset_forget(ts, false);
     ts->mwu_few_ties = -1;
-    for (auto &kv : ts->windows) kv.second.indexed = false;     // every width's index describes the old data
     if (!ts->owns && !ts->pipe_mode) {
         // zero-copy track set rewritten in place: its runs may start earlier / end later than
         // before, so the extents, their check and every width's window tables are rebuilt too
@@ -933,7 +734,7 @@ int wtamd_trackset_index(wtamd_trackset *ts, int op, void *stream) {
     return wt_build_index(ts, w, plan, (hipStream_t) stream);
 }
 
-static int wt_check_desc(const wtamd_trackset *ts, const wtamd_reduce_desc *d) {
+extern "C++" int wt_check_desc(const wtamd_trackset *ts, const wtamd_reduce_desc *d) {
     if (!ts || !d) return wt_fail(WTAMD_ERR_ARG, "NULL argument");
     if (d->op < 0 || d->op >= WTAMD_OP_COUNT_) return wt_fail(WTAMD_ERR_ARG, "unknown op");
     if (d->op == WTAMD_OP_TTEST) {
@@ -953,12 +754,12 @@ static int wt_reduce_plan(wtamd_trackset *ts, const WtPlan &plan, int op, uint32
 
 // The general kernel over the `n_bad` windows the difference-array launch (window width delta_W,
 // just finished or still running on `s`) recorded as not provably exact.
-static int wt_launch_patch(wtamd_trackset *ts, int delta_W, int op, uint32_t flags, int n_set0, wtamd_runs *runs, long long n_bad,
-                           hipStream_t s) {
+extern "C++" int wt_launch_patch(wtamd_trackset *ts, int delta_W, int op, uint32_t flags, int n_set0, wtamd_runs *runs, long long n_bad,
+                                 hipStream_t s) {
     WtPlan plan;
     std::string err;
     if (!wt_make_plan(ts->n_tracks, op, ts->scratch_f32, plan, err)) return wt_fail(WTAMD_ERR_INTERNAL, err);
-    if (plan.scratch_slab > 0 || plan.W > delta_W || delta_W % plan.W != 0 || delta_W / plan.W > WT_BAD_SUB || !ts->scratch_f32 || ts->value_f64)
+    if (!wt_patch_compatible(plan, delta_W, ts->scratch_f32, ts->value_f64))
         return wt_fail(WTAMD_ERR_INTERNAL, "no general plan compatible with the difference-array windows (general W " + std::to_string(plan.W) + ", difference-array W " +
                        std::to_string(delta_W) + ", slab " + std::to_string((long long) plan.scratch_slab) + ", float staging " + std::to_string((int) ts->scratch_f32) + ", f64 values " +
                        std::to_string((int) ts->value_f64) + ")");
@@ -1020,7 +821,7 @@ static int wt_reduce_impl(wtamd_trackset *ts, int op, uint32_t flags, int n_set0
         if (rc != WTAMD_OK && rc != WTAMD_ERR_CAPACITY) return rc;
         const long long n_bad = (long long) ts->h_counters[WT_CTR_DELTA_BAD];
         if (n_bad == 0) { ts->delta_verified_[dc] = true; ts->delta_n_bad_[dc] = 0; return rc; }
-        if (n_bad * 4 <= (long long) ts->stats.n_windows && !getenv("WTAMD_NO_PATCH")) {
+        if (wt_few_enough_to_patch(n_bad, ts->stats.n_windows) && !getenv("WTAMD_NO_PATCH")) {
             const int rp = wt_launch_patch(ts, plan.W, op, flags, n_set0, runs, n_bad, s);
             if (rp == WTAMD_OK) {
                 WT_HIP(hipStreamSynchronize(s));
@@ -1034,6 +835,20 @@ static int wt_reduce_impl(wtamd_trackset *ts, int op, uint32_t flags, int n_set0
     }
     if (!wt_pick_plan(ts, op, n_set0, plan, err, s)) return wt_fail(WTAMD_ERR_ARG, err);
     return wt_reduce_plan(ts, plan, op, flags, n_set0, runs, d_tile, d_inplay, n_runs, s);
+}
+
+extern "C++" int wt_reduce_enqueue(wtamd_trackset *ts, const wtamd_reduce_desc &desc, wtamd_runs *runs, double *d_tile, uint8_t *d_inplay,
+                                   hipStream_t s, bool *used_delta, int *delta_W) {
+    WtPlan plan;
+    std::string err;
+    *used_delta = !d_tile && wt_wants_delta(ts, desc.op);
+    if (*used_delta) {
+        wt_make_delta_plan_for(plan, ts->n_tracks, desc.op);
+        *delta_W = plan.W;
+    } else if (!wt_pick_plan(ts, desc.op, desc.n_set0, plan, err, s)) {
+        return wt_fail(WTAMD_ERR_ARG, err);
+    }
+    return wt_reduce_plan(ts, plan, desc.op, desc.flags, desc.n_set0, runs, d_tile, d_inplay, nullptr, s);
 }
 
 static int wt_reduce_plan(wtamd_trackset *ts, const WtPlan &plan, int op, uint32_t flags, int n_set0, wtamd_runs *runs,
@@ -1115,29 +930,14 @@ static int wt_reduce_plan(wtamd_trackset *ts, const WtPlan &plan, int op, uint32
     ts->stats.patched_windows = 0;
     if (n_runs) {
         WT_HIP(hipMemcpyAsync(ts->h_counters, ts->d_counters, sizeof(unsigned long long) * WT_CTR_N, hipMemcpyDeviceToHost, s));
-        {
-            // bounded wait: a kernel that does not finish is reported, never waited for forever
-            const double limit_s = getenv("WTAMD_TIMEOUT_S") ? atof(getenv("WTAMD_TIMEOUT_S")) : 120.0;
-            const auto t0 = std::chrono::steady_clock::now();
-            for (;;) {
-                const hipError_t q = hipStreamQuery(s);
-                if (q == hipSuccess) break;
-                if (q != hipErrorNotReady) return wt_fail(WTAMD_ERR_HIP, std::string("hipStreamQuery: ") + hipGetErrorString(q));
-                const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-                if (el > limit_s) {
-                    char buf[320];
-                    snprintf(buf, sizeof buf, "kernel did not finish within %.0f s (debug marker %llu, window %lld; per wave %llu %llu %llu %llu %llu %llu %llu %llu)",
-                             limit_s, ts->h_debug[0], (long long) ts->h_debug[1], ts->h_debug[2], ts->h_debug[3], ts->h_debug[4],
-                             ts->h_debug[5], ts->h_debug[6], ts->h_debug[7], ts->h_debug[8], ts->h_debug[9]);
-                    // a kernel that never finishes cannot be cancelled and every later HIP call of this
-                    // process (even hipFree) would block behind it: report and terminate the process
-                    fprintf(stderr, "wiggletools_amd: FATAL: %s\n", buf);
-                    fflush(stderr);
-                    _exit(70);
-                }
-                if (el > 0.002) std::this_thread::sleep_for(std::chrono::microseconds(200));
-            }
-        }
+        const int rcw = wt_bounded_wait([s] { return hipStreamQuery(s); }, "hipStreamQuery", nullptr, 0.002, 200, [ts](double limit_s) {
+            char buf[320];
+            snprintf(buf, sizeof buf, "kernel did not finish within %.0f s (debug marker %llu, window %lld; per wave %llu %llu %llu %llu %llu %llu %llu %llu)",
+                     limit_s, ts->h_debug[0], (long long) ts->h_debug[1], ts->h_debug[2], ts->h_debug[3], ts->h_debug[4],
+                     ts->h_debug[5], ts->h_debug[6], ts->h_debug[7], ts->h_debug[8], ts->h_debug[9]);
+            return std::string(buf);
+        });
+        if (rcw != WTAMD_OK) return rcw;
         ts->stats.n_runs = (int64_t) ts->h_counters[WT_CTR_RUNS];
         ts->stats.covered_bp = (int64_t) ts->h_counters[WT_CTR_BP];
         ts->stats.n_intervals = (int64_t) ts->h_counters[WT_CTR_INTERVALS];
@@ -1236,12 +1036,9 @@ static int wt_runs_auc_span(const wtamd_runs *runs, int64_t n_runs, double *auc,
     const int blocks = 512;
     double *d_partial = nullptr, h[2] = {0, 0};
     WtDevScope scope;
-    WT_HIP(scope.alloc(&d_partial, sizeof(double) * (2 * blocks + 2)));
-    hipLaunchKernelGGL(wt_auc_kernel, dim3(blocks), dim3(256), 0, s, runs->start, runs->finish, runs->value,
-                       (long long) n_runs, d_partial, span ? d_partial + blocks : nullptr);
-    hipLaunchKernelGGL(wt_auc_final_kernel, dim3(1), dim3(64), 0, s, d_partial, blocks, d_partial + 2 * blocks);
-    if (span) hipLaunchKernelGGL(wt_auc_final_kernel, dim3(1), dim3(64), 0, s, d_partial + blocks, blocks, d_partial + 2 * blocks + 1);
-    WT_HIP(hipGetLastError());
+    WT_HIP(scope.alloc(&d_partial, wt_auc_partial_bytes(blocks) + sizeof(double) * 2));
+    const int rc = wt_auc_async(runs->start, runs->finish, runs->value, (long long) n_runs, nullptr, blocks, d_partial, d_partial + 2 * blocks, span != nullptr, s);
+    if (rc != WTAMD_OK) return rc;
     WT_HIP(hipMemcpyAsync(h, d_partial + 2 * blocks, sizeof(double) * (span ? 2 : 1), hipMemcpyDeviceToHost, s));
     WT_HIP(hipStreamSynchronize(s));
     *auc = h[0];
@@ -1272,7 +1069,7 @@ static int wt_pearson_impl(wtamd_trackset *ts, double *result7) {
     d.capacity = cap;
     double *d_tile = nullptr;
     uint8_t *d_inplay = nullptr;
-    WtMoments *d_partial = nullptr;
+    char *d_partial = nullptr;
     double *d_out = nullptr;
     const int blocks = 256;
     WtDevScope scope;
@@ -1282,15 +1079,13 @@ static int wt_pearson_impl(wtamd_trackset *ts, double *result7) {
     WT_HIP(scope.alloc(&d.chrom_run_off, sizeof(int64_t) * (ts->n_chrom + 1)));
     WT_HIP(scope.alloc(&d_tile, sizeof(double) * alloc * 2));
     WT_HIP(scope.alloc(&d_inplay, sizeof(uint8_t) * alloc * 2));
-    WT_HIP(scope.alloc(&d_partial, sizeof(WtMoments) * blocks));
+    WT_HIP(scope.alloc(&d_partial, wt_pearson_partial_bytes(blocks)));
     WT_HIP(scope.alloc(&d_out, sizeof(double) * 7));
     int64_t n = 0;
     int rc = wt_reduce_impl(ts, WT_OP_MULTIPLEX, 0, 0, &d, d_tile, d_inplay, &n, nullptr);
     if (rc == WTAMD_OK) {
-        hipLaunchKernelGGL(wt_pearson_kernel, dim3(blocks), dim3(256), 0, nullptr, d.start, d.finish, d_tile, d_inplay,
-                           ts->defaults[0], ts->defaults[1], (long long) n, d_partial);
-        hipLaunchKernelGGL(wt_pearson_final_kernel, dim3(1), dim3(64), 0, nullptr, d_partial, blocks, d_out);
-        if (hipGetLastError() != hipSuccess || hipMemcpy(result7, d_out, sizeof(double) * 7, hipMemcpyDeviceToHost) != hipSuccess)
+        rc = wt_pearson_async(d.start, d.finish, d_tile, d_inplay, ts->defaults[0], ts->defaults[1], (long long) n, nullptr, blocks, d_partial, d_out, nullptr);
+        if (rc != WTAMD_OK || hipMemcpy(result7, d_out, sizeof(double) * 7, hipMemcpyDeviceToHost) != hipSuccess)
             rc = wt_fail(WTAMD_ERR_HIP, "wtamd_pearson: kernel launch / copy failed");
     }
     return rc;
@@ -1346,4 +1141,3 @@ int wtamd_get_stats(const wtamd_trackset *ts_c, wtamd_stats *out) {
 
 }  // extern "C"
 
-#include "wt_pipe.h"

@@ -1,5 +1,5 @@
-// wt_kernels.h -- what the host side (wt_engine.hip) needs of the kernel units: the launch record, the patch kernel's
-// arguments, the kernels' launch bounds and one launch entry per kernel family.  The kernels are templates in
+// wt_kernels.h -- what the engine (wt_engine.hip; the pipeline reaches the kernels through it, wt_trackset.h) needs of the
+// kernel units: the launch record, the patch kernel's arguments, the kernels' launch bounds and one launch entry per kernel family.  The kernels are templates in
 // wt_reduce_kernel.h / wt_delta_kernel.h, instantiated by op in wt_reduce_stream.hip, wt_reduce_moments.hip,
 // wt_reduce_order.hip, wt_patch_kernels.hip and wt_delta_kernels.hip; wt_walk.hip holds the walking kernels.
 #ifndef WT_KERNELS_H_

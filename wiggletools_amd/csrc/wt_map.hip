@@ -19,16 +19,13 @@
 #include <string>
 #include <vector>
 
-#include "../../include/wiggletools_amd.h"
+#include "wt_host.h"
 #include "wt_devscope.h"
 #include "wt_mapop.h"
 
 #define WM_BLOCK 256
 #define WM_ITEMS 16
 #define WM_TILE (WM_BLOCK * WM_ITEMS)
-
-extern "C" const char *wtamd_last_error(void);
-int wt_fail_ext(int code, const std::string &msg);     // wt_engine.hip
 
 namespace {
 
@@ -301,13 +298,13 @@ int wt_map_upload_chains(const wtamd_map_chain *chains, int n_tracks, void **d_o
     }
     for (int t = 0; t < n_tracks; t++) {
         const wtamd_map_chain &c = chains[t];
-        if (c.n_ops < 0 || c.n_ops > WTAMD_MAP_CHAIN_MAX) return wt_fail_ext(WTAMD_ERR_ARG, "wtamd_pipe_set_map: chain length");
+        if (c.n_ops < 0 || c.n_ops > WTAMD_MAP_CHAIN_MAX) return wt_fail(WTAMD_ERR_ARG, "wtamd_pipe_set_map: chain length");
         h[(size_t) t].n_ops = c.n_ops;
         for (int k = 0; k < WTAMD_MAP_CHAIN_MAX; k++) {
             const int op = k < c.n_ops ? c.op[k] : WTAMD_MAP_COUNT_;
-            if (k < c.n_ops && (op < 0 || op >= WTAMD_MAP_COUNT_)) return wt_fail_ext(WTAMD_ERR_ARG, "wtamd_pipe_set_map: unknown operator");
+            if (k < c.n_ops && (op < 0 || op >= WTAMD_MAP_COUNT_)) return wt_fail(WTAMD_ERR_ARG, "wtamd_pipe_set_map: unknown operator");
             if (k < c.n_ops && (op == WTAMD_MAP_LOG || op == WTAMD_MAP_EXPB) && !(c.param[k] > 0))
-                return wt_fail_ext(WTAMD_ERR_ARG, "wtamd_pipe_set_map: base / radix must be positive");
+                return wt_fail(WTAMD_ERR_ARG, "wtamd_pipe_set_map: base / radix must be positive");
             h[(size_t) t].op[k] = op;
             h[(size_t) t].param[k] = k < c.n_ops ? c.param[k] : 0;
             h[(size_t) t].lg[k] = (op == WTAMD_MAP_LOG || op == WTAMD_MAP_EXPB) ? log(c.param[k]) : 1.0;
@@ -315,10 +312,10 @@ int wt_map_upload_chains(const wtamd_map_chain *chains, int n_tracks, void **d_o
         }
     }
     void *d = nullptr;
-    if (hipMalloc(&d, sizeof(WmChain) * (size_t) n_tracks) != hipSuccess) return wt_fail_ext(WTAMD_ERR_HIP, "hipMalloc(map chains)");
+    if (hipMalloc(&d, sizeof(WmChain) * (size_t) n_tracks) != hipSuccess) return wt_fail(WTAMD_ERR_HIP, "hipMalloc(map chains)");
     if (hipMemcpy(d, h.data(), sizeof(WmChain) * (size_t) n_tracks, hipMemcpyHostToDevice) != hipSuccess) {
         (void) hipFree(d);
-        return wt_fail_ext(WTAMD_ERR_HIP, "hipMemcpy(map chains)");
+        return wt_fail(WTAMD_ERR_HIP, "hipMemcpy(map chains)");
     }
     *d_out = d;
     return WTAMD_OK;
@@ -326,16 +323,13 @@ int wt_map_upload_chains(const wtamd_map_chain *chains, int n_tracks, void **d_o
 
 extern "C" {
 
-#define WM_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) \
-    return wt_fail_ext(WTAMD_ERR_HIP, std::string(#call ": ") + hipGetErrorString(e_)); } while (0)
-
 int wtamd_runs_map(int map_op, double param, int64_t n_seg, const int64_t *seg_off, const int32_t *start,
                    const int32_t *finish, const void *value, int value_is_f64, int32_t *o_start, int32_t *o_finish,
                    double *o_value, int64_t *o_seg_off, void *stream) {
     if (map_op < 0 || map_op >= WTAMD_MAP_COUNT_ || n_seg < 0 || !seg_off || !o_value || !o_seg_off)
-        return wt_fail_ext(WTAMD_ERR_ARG, "wtamd_runs_map: bad argument");
+        return wt_fail(WTAMD_ERR_ARG, "wtamd_runs_map: bad argument");
     if ((map_op == WTAMD_MAP_LOG || map_op == WTAMD_MAP_EXPB) && !(param > 0))
-        return wt_fail_ext(WTAMD_ERR_ARG, "wtamd_runs_map: base / radix must be positive");
+        return wt_fail(WTAMD_ERR_ARG, "wtamd_runs_map: base / radix must be positive");
     hipStream_t s = (hipStream_t) stream;
     const long long n = seg_off[n_seg];
     const bool drops = map_op == WTAMD_MAP_LN || map_op == WTAMD_MAP_LOG || map_op >= WTAMD_MAP_GT;
@@ -350,11 +344,11 @@ int wtamd_runs_map(int map_op, double param, int64_t n_seg, const int64_t *seg_o
     int64_t *d_seg = nullptr, *d_oseg = nullptr;
     WtDevScope scope;
     if (drops) {
-        WM_HIP(scope.alloc(&d_blk, sizeof(unsigned long long) * (n_blocks + 1)));
-        WM_HIP(scope.alloc(&d_mapped, sizeof(double) * n));
-        WM_HIP(scope.alloc(&d_seg, sizeof(int64_t) * (n_seg + 1) * 2));
+        WT_HIP(scope.alloc(&d_blk, sizeof(unsigned long long) * (n_blocks + 1)));
+        WT_HIP(scope.alloc(&d_mapped, sizeof(double) * n));
+        WT_HIP(scope.alloc(&d_seg, sizeof(int64_t) * (n_seg + 1) * 2));
         d_oseg = d_seg + (n_seg + 1);
-        WM_HIP(hipMemcpyAsync(d_seg, seg_off, sizeof(int64_t) * (n_seg + 1), hipMemcpyHostToDevice, s));
+        WT_HIP(hipMemcpyAsync(d_seg, seg_off, sizeof(int64_t) * (n_seg + 1), hipMemcpyHostToDevice, s));
     }
     if (value_is_f64)
         hipLaunchKernelGGL(wm_map_kernel<double>, dim3((unsigned) n_blocks), dim3(WM_BLOCK), 0, s, map_op, param, lg,
@@ -362,20 +356,20 @@ int wtamd_runs_map(int map_op, double param, int64_t n_seg, const int64_t *seg_o
     else
         hipLaunchKernelGGL(wm_map_kernel<float>, dim3((unsigned) n_blocks), dim3(WM_BLOCK), 0, s, map_op, param, lg,
                            (const float *) value, n, d_mapped, d_blk);
-    WM_HIP(hipGetLastError());
+    WT_HIP(hipGetLastError());
     if (!drops) {
         // coordinates are unchanged: copy them only if the caller asked for separate arrays
-        if (o_start && o_start != start) WM_HIP(hipMemcpyAsync(o_start, start, sizeof(int32_t) * n, hipMemcpyDeviceToDevice, s));
-        if (o_finish && o_finish != finish) WM_HIP(hipMemcpyAsync(o_finish, finish, sizeof(int32_t) * n, hipMemcpyDeviceToDevice, s));
-        WM_HIP(hipStreamSynchronize(s));
+        if (o_start && o_start != start) WT_HIP(hipMemcpyAsync(o_start, start, sizeof(int32_t) * n, hipMemcpyDeviceToDevice, s));
+        if (o_finish && o_finish != finish) WT_HIP(hipMemcpyAsync(o_finish, finish, sizeof(int32_t) * n, hipMemcpyDeviceToDevice, s));
+        WT_HIP(hipStreamSynchronize(s));
         for (int64_t q = 0; q <= n_seg; q++) o_seg_off[q] = seg_off[q];
         return WTAMD_OK;
     }
-    if (!o_start || !o_finish) return wt_fail_ext(WTAMD_ERR_ARG, "wtamd_runs_map: operators that drop runs need output coordinate arrays");
+    if (!o_start || !o_finish) return wt_fail(WTAMD_ERR_ARG, "wtamd_runs_map: operators that drop runs need output coordinate arrays");
     hipLaunchKernelGGL(wm_scan_blocks, dim3(1), dim3(64), 0, s, d_blk, n_blocks, d_blk + n_blocks);
     unsigned long long total = 0;
-    WM_HIP(hipMemcpyAsync(&total, d_blk + n_blocks, sizeof total, hipMemcpyDeviceToHost, s));
-    WM_HIP(hipStreamSynchronize(s));
+    WT_HIP(hipMemcpyAsync(&total, d_blk + n_blocks, sizeof total, hipMemcpyDeviceToHost, s));
+    WT_HIP(hipStreamSynchronize(s));
     const unsigned seg_grid = (unsigned) ((n_seg + 1 + 255) / 256);
     if (value_is_f64) {
         hipLaunchKernelGGL(wm_compact_kernel<double>, dim3((unsigned) n_blocks), dim3(WM_BLOCK), 0, s, map_op, param,
@@ -388,9 +382,9 @@ int wtamd_runs_map(int map_op, double param, int64_t n_seg, const int64_t *seg_o
         hipLaunchKernelGGL(wm_seg_offsets<float>, dim3(seg_grid), dim3(256), 0, s, map_op, param, (const float *) value, d_seg,
                            (long long) n_seg, n, d_blk, total, d_oseg);
     }
-    WM_HIP(hipGetLastError());
-    WM_HIP(hipMemcpyAsync(o_seg_off, d_oseg, sizeof(int64_t) * (n_seg + 1), hipMemcpyDeviceToHost, s));
-    WM_HIP(hipStreamSynchronize(s));
+    WT_HIP(hipGetLastError());
+    WT_HIP(hipMemcpyAsync(o_seg_off, d_oseg, sizeof(int64_t) * (n_seg + 1), hipMemcpyDeviceToHost, s));
+    WT_HIP(hipStreamSynchronize(s));
     return WTAMD_OK;
 }
 

@@ -1,4 +1,7 @@
-// wt_moments.hip -- the genome-wide statistics that need more than a sum, in ONE pass over a device run list:
+// wt_moments.hip -- the integrators: genome-wide statistics of a device run list, each behind an asynchronous entry
+// (wt_host.h) that the bulk doors (wt_engine.hip) and the streaming pipeline (wt_pipe.hip) launch with their own block
+// counts.  Further down: wt_auc_kernel (AUC, meanI) and wt_pearson_kernel (Pearson of a 2-track Multiplexer tile).  First
+// the statistics that need more than a sum, in ONE pass:
 // varI / stddevI / CVI, maxI / minI and the span (reference src/statistics.c:129-326).  One launch yields
 //
 //     { sum = S L v,  span = S L,  T = S L (v - sum/span)^2,  min,  max,  spare }      L = finish - start,
@@ -23,10 +26,8 @@
 #include <cstdint>
 #include <string>
 
-#include "../../include/wiggletools_amd.h"
+#include "wt_host.h"
 #include "wt_devscope.h"
-
-int wt_fail_ext(int code, const std::string &msg);     // wt_engine.hip
 
 namespace {
 
@@ -177,6 +178,158 @@ __global__ void __launch_bounds__(WM_BLOCK) wt_moments_final_kernel(const WmPart
 
 }  // namespace
 
+// AUC: statistics.c:103-120.  Deterministic two-level sum.
+__global__ void __launch_bounds__(256) wt_auc_kernel(const int32_t *start, const int32_t *finish, const double *value,
+                                                      long long n, double *partial, double *partial_span,
+                                                      const unsigned long long *n_dev = nullptr) {
+    __shared__ double red[256];
+    double acc = 0, span = 0;
+    if (n_dev && (long long) *n_dev < n) n = (long long) *n_dev;       // (pipeline: the run count only exists on the device)
+    const long long stride = (long long) gridDim.x * blockDim.x;
+    for (long long r = (long long) blockIdx.x * blockDim.x + threadIdx.x; r < n; r += stride) {
+        const double v = value[r];
+        if (v == v) {                                   // NaN runs are skipped (statistics.c:78, 110)
+            const double len = (double) (finish[r] - start[r]);
+            acc += len * v;
+            span += len;
+        }
+    }
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int) threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+    if (partial_span) {                                 // MeanIntegrator also needs the non-NaN span
+        __syncthreads();
+        red[threadIdx.x] = span;
+        __syncthreads();
+        for (int s = 128; s > 0; s >>= 1) {
+            if ((int) threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) partial_span[blockIdx.x] = red[0];
+    }
+}
+
+__global__ void wt_auc_final_kernel(const double *partial, int n, double *out) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        double acc = 0;
+        for (int i = 0; i < n; i++) acc += partial[i];
+        *out = acc;
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Pearson correlation of two tracks over the Multiplexer tile (reference PearsonIntegrator,
+// statistics.c:414-465).  The reference updates {count, sum, T_XX, T_XY, T_YY} run by run with the
+// weighted Welford / Chan step (its `new_mean` is old sum / new count; expanding
+// n*L/(n+L) * (X - mean)^2 gives exactly its expression).  Here every lane applies that step IN ITS
+// UNEXPANDED FORM, n*L/(n+L) * (X - mean)^2, to a contiguous slice of runs, and slices are merged
+// pairwise in genome order with the same formula for two aggregates -- mathematically identical.
+// The expanded form sums terms of size mean^2 to get one of size deviation^2; in the reference's one long
+// pass that costs (mean/deviation)^2 of the digits with errors of either sign, but at the start of
+// every slice -- 65 536 of them, n / (n + L) far from 1 -- the errors are biased: on a track of
+// relative variance 1e-10 (70 001 runs) T_XX came out 2.1e-8 off where the reference's own pass is
+// 4.9e-10 off; unexpanded it is 2.9e-13 off (tests/test_side_kernels.py::test_gpu_pearson_constant_track_rule,
+// against exact rational arithmetic; the other tests hold 1e-9 against the oracle).
+// ---------------------------------------------------------------------------
+struct WtMoments {
+    double n, sx, sy, txx, txy, tyy;
+};
+
+__device__ inline void wt_moments_add_run(WtMoments &m, double X, double Y, double L) {
+    if (m.n > 0) {
+        const double dx = X - m.sx / m.n, dy = Y - m.sy / m.n;
+        const double w = m.n * L / (m.n + L);
+        m.txx += dx * dx * w;
+        m.txy += dx * dy * w;
+        m.tyy += dy * dy * w;
+    }
+    m.n += L;
+    m.sx += X * L;
+    m.sy += Y * L;
+}
+
+// a := a (+) b, b following a in genome order
+__device__ inline void wt_moments_merge(WtMoments &a, const WtMoments &b) {
+    if (b.n == 0) return;
+    if (a.n == 0) { a = b; return; }
+    const double n = a.n + b.n;
+    const double dx = b.sx / b.n - a.sx / a.n, dy = b.sy / b.n - a.sy / a.n;
+    const double w = a.n * b.n / n;
+    a.txx += b.txx + dx * dx * w;
+    a.txy += b.txy + dx * dy * w;
+    a.tyy += b.tyy + dy * dy * w;
+    a.n = n;
+    a.sx += b.sx;
+    a.sy += b.sy;
+}
+
+__global__ void __launch_bounds__(256) wt_pearson_kernel(const int32_t *start, const int32_t *finish, const double *tile,
+                                                          const uint8_t *inplay, double dx, double dy, long long n,
+                                                          WtMoments *partial, const unsigned long long *n_dev = nullptr) {
+    __shared__ WtMoments red[256];
+    if (n_dev && (long long) *n_dev < n) n = (long long) *n_dev;
+    const long long total_lanes = (long long) gridDim.x * blockDim.x;
+    const long long per = (n + total_lanes - 1) / total_lanes;          // contiguous slice per lane
+    const long long lane_id = (long long) blockIdx.x * blockDim.x + threadIdx.x;
+    long long lo = lane_id * per, hi = lo + per;
+    if (hi > n) hi = n;
+    WtMoments m = {0, 0, 0, 0, 0, 0};
+    for (long long r = lo; r < hi; r++) {
+        const double X = inplay[2 * r] ? tile[2 * r] : dx;
+        const double Y = inplay[2 * r + 1] ? tile[2 * r + 1] : dy;
+        wt_moments_add_run(m, X, Y, (double) (finish[r] - start[r]));
+    }
+    red[threadIdx.x] = m;
+    __syncthreads();
+    for (int s = 1; s < 256; s <<= 1) {                                 // ordered pairwise merge
+        if ((threadIdx.x & (2 * s - 1)) == 0) wt_moments_merge(red[threadIdx.x], red[threadIdx.x + s]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+}
+
+__global__ void wt_pearson_final_kernel(const WtMoments *partial, int n, double *out) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        WtMoments m = {0, 0, 0, 0, 0, 0};
+        for (int i = 0; i < n; i++) wt_moments_merge(m, partial[i]);
+        double txx = m.txx, tyy = m.tyy;                               // (constant track: see wtamd_pearson_finish)
+        if (m.n > 0) {
+            const double mx = m.sx / m.n, my = m.sy / m.n;
+            if (txx <= m.n * mx * mx * 1e-14) txx = 0;
+            if (tyy <= m.n * my * my * 1e-14) tyy = 0;
+        }
+        const double den = txx * tyy;
+        out[0] = den ? m.txy / sqrt(den) : __builtin_nan("");          // statistics.c:421-423
+        out[1] = m.n; out[2] = m.sx; out[3] = m.sy; out[4] = m.txx; out[5] = m.txy; out[6] = m.tyy;
+    }
+}
+
+size_t wt_auc_partial_bytes(int blocks) { return sizeof(double) * 2 * (size_t) blocks; }
+
+int wt_auc_async(const int32_t *start, const int32_t *finish, const double *value, long long n, const unsigned long long *n_dev,
+                 int blocks, void *d_partial, double *d_out, bool with_span, hipStream_t st) {
+    double *part = (double *) d_partial;
+    hipLaunchKernelGGL(wt_auc_kernel, dim3(blocks), dim3(256), 0, st, start, finish, value, n, part, with_span ? part + blocks : nullptr, n_dev);
+    hipLaunchKernelGGL(wt_auc_final_kernel, dim3(1), dim3(64), 0, st, part, blocks, d_out);
+    if (with_span) hipLaunchKernelGGL(wt_auc_final_kernel, dim3(1), dim3(64), 0, st, part + blocks, blocks, d_out + 1);
+    WT_HIP(hipGetLastError());
+    return WTAMD_OK;
+}
+
+size_t wt_pearson_partial_bytes(int blocks) { return sizeof(WtMoments) * (size_t) blocks; }
+
+int wt_pearson_async(const int32_t *start, const int32_t *finish, const double *tile, const uint8_t *inplay, double dx, double dy, long long n,
+                     const unsigned long long *n_dev, int blocks, void *d_partial, double *d_out7, hipStream_t st) {
+    hipLaunchKernelGGL(wt_pearson_kernel, dim3(blocks), dim3(256), 0, st, start, finish, tile, inplay, dx, dy, n, (WtMoments *) d_partial, n_dev);
+    hipLaunchKernelGGL(wt_pearson_final_kernel, dim3(1), dim3(64), 0, st, (const WtMoments *) d_partial, blocks, d_out7);
+    WT_HIP(hipGetLastError());
+    return WTAMD_OK;
+}
+
 // Moments of the run list -> d_out6 (device), on `st`.  d_partial: wt_moments_partial_bytes(blocks) bytes of device memory.
 size_t wt_moments_partial_bytes(int blocks) { return sizeof(WmPartial) * (size_t) blocks; }
 
@@ -185,11 +338,11 @@ int wt_moments_async(const int32_t *start, const int32_t *finish, const double *
     hipLaunchKernelGGL(wt_moments_kernel, dim3((unsigned) blocks), dim3(WM_BLOCK), 0, st, start, finish, value, cap, n_dev,
                        (WmPartial *) d_partial);
     hipLaunchKernelGGL(wt_moments_final_kernel, dim3(1), dim3(WM_BLOCK), 0, st, (const WmPartial *) d_partial, blocks, d_out6);
-    return hipGetLastError() == hipSuccess ? WTAMD_OK : wt_fail_ext(WTAMD_ERR_HIP, "moments kernel launch failed");
+    return hipGetLastError() == hipSuccess ? WTAMD_OK : wt_fail(WTAMD_ERR_HIP, "moments kernel launch failed");
 }
 
 extern "C" int wtamd_runs_moments(const wtamd_runs *runs, int64_t n_runs, double *moments6, void *stream) {
-    if (!runs || !moments6 || n_runs < 0) return wt_fail_ext(WTAMD_ERR_ARG, "wtamd_runs_moments: bad argument");
+    if (!runs || !moments6 || n_runs < 0) return wt_fail(WTAMD_ERR_ARG, "wtamd_runs_moments: bad argument");
     hipStream_t st = (hipStream_t) stream;
     // enough lanes to keep every CU's loads in flight, few enough that the ordered tail stays short
     long long want = (n_runs + 2 * WM_BLOCK * 4 - 1) / (2 * WM_BLOCK * 4);
@@ -197,11 +350,11 @@ extern "C" int wtamd_runs_moments(const wtamd_runs *runs, int64_t n_runs, double
     char *d = nullptr;
     WtDevScope scope;
     if (scope.alloc(&d, wt_moments_partial_bytes(blocks) + sizeof(double) * 6) != hipSuccess)
-        return wt_fail_ext(WTAMD_ERR_HIP, "wtamd_runs_moments: out of device memory");
+        return wt_fail(WTAMD_ERR_HIP, "wtamd_runs_moments: out of device memory");
     double *d_out = (double *) (d + wt_moments_partial_bytes(blocks));
     const int rc = wt_moments_async(runs->start, runs->finish, runs->value, (long long) n_runs, nullptr, blocks, d, d_out, st);
     if (rc != WTAMD_OK) return rc;
     if (hipMemcpyAsync(moments6, d_out, sizeof(double) * 6, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-        return wt_fail_ext(WTAMD_ERR_HIP, "wtamd_runs_moments: copy failed");
+        return wt_fail(WTAMD_ERR_HIP, "wtamd_runs_moments: copy failed");
     return WTAMD_OK;
 }

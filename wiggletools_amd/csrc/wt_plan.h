@@ -571,4 +571,32 @@ static inline bool wt_defaults_fit_f32(const double *d, int n) {
     return true;
 }
 
+// ---------------------------------------------------------------------------
+// The reduction policy, stated once for the engine, the pipeline and the emulator: difference-array plan first
+// (wt_delta_eligible), its few inexact windows patched by the general kernel, many redone by it -- and which general plan.
+// ---------------------------------------------------------------------------
+// The general (non difference-array) plan: MedianReduction over float tracks walks (wt_walk.h) when `median_walk`,
+// MWUReduction walks (wt_mwalk.h) when the caller decided so (`mwu_walk`: by a switch or by the values), everything else --
+// and either of them when no walk plan fits -- takes the bitmap kernel (same domain as the register columns,
+// wt_regcol_slots: float tracks, float-exact defaults, at most 64 per set).  events_per_bp sizes the walks' slots.
+static inline bool wt_pick_general_plan(int n_tracks, int op, bool value_f64, bool scratch_f32, int n_set0, bool median_walk, bool mwu_walk,
+                                        double events_per_bp, WtPlan &plan, std::string &err) {
+    if (op == WT_OP_MEDIAN && !value_f64 && median_walk)
+        if (const int nr = wt_regcol_slots(n_tracks, op, scratch_f32, n_set0))
+            if (wt_make_walk_plan(plan, n_tracks, nr, events_per_bp)) return true;
+    if (op == WT_OP_MWU && !value_f64 && mwu_walk)
+        if (const int nr = wt_regcol_slots(n_tracks, op, scratch_f32, n_set0))
+            if (wt_make_walk_plan(plan, n_tracks, nr, events_per_bp, 160 * 1024, n_set0)) return true;
+    return wt_make_plan(n_tracks, op, scratch_f32, plan, err, 80 * 1024, 160 * 1024, n_set0);
+}
+
+// Can the general plan rewrite single windows of a difference-array launch of width delta_W (the patch kernel)?  Its windows
+// must tile the wider ones (at most WT_BAD_SUB each), its columns live in LDS, and the staging is the float one.
+static inline bool wt_patch_compatible(const WtPlan &general, int delta_W, bool scratch_f32, bool value_f64) {
+    return !(general.scratch_slab > 0 || general.W > delta_W || delta_W % general.W != 0 || delta_W / general.W > WT_BAD_SUB || !scratch_f32 || value_f64);
+}
+
+// Few enough inexact windows to patch them; more, and the whole launch is redone by the general kernel.
+static inline bool wt_few_enough_to_patch(long long n_bad, long long n_windows) { return n_bad * 4 <= n_windows; }
+
 #endif  // WT_PLAN_H_

@@ -19,10 +19,8 @@
 #include <string>
 #include <vector>
 
-#include "../../include/wiggletools_amd.h"
+#include "wt_host.h"
 #include "wt_devscope.h"
-
-int wt_fail_ext(int code, const std::string &msg);     // wt_engine.hip
 
 #define WS_BLOCK 256
 #define WS_PER_LANE 16
@@ -168,14 +166,14 @@ __global__ void __launch_bounds__(WS_BLOCK) ws_fill_kernel(const WsArgs A, const
 int ws_args(unsigned long long seed, int n_chrom, const int32_t *chrom_len, int n_tracks, double mean_run, double gap_prob,
             int levels, WsArgs &A, long long &n_blocks) {
     if (n_chrom <= 0 || n_chrom > WS_MAX_CHROM || !chrom_len || n_tracks <= 0 || mean_run < 1.0 || levels <= 0 || gap_prob < 0 || gap_prob >= 1)
-        return wt_fail_ext(WTAMD_ERR_ARG, "wtamd_synth: bad arguments");
+        return wt_fail(WTAMD_ERR_ARG, "wtamd_synth: bad arguments");
     A.seed = seed; A.n_chrom = n_chrom; A.n_tracks = n_tracks;
     A.bp_thresh = mean_run <= 1.0 ? 0u : (uint32_t) (4294967296.0 / mean_run);
     A.gap_thresh = (uint32_t) (4294967296.0 * gap_prob);
     A.levels = (uint32_t) levels;
     long long off = 0;
     for (int c = 0; c < n_chrom; c++) {
-        if (chrom_len[c] <= 0) return wt_fail_ext(WTAMD_ERR_ARG, "wtamd_synth: chromosome length must be positive");
+        if (chrom_len[c] <= 0) return wt_fail(WTAMD_ERR_ARG, "wtamd_synth: chromosome length must be positive");
         A.chrom_len[c] = chrom_len[c];
         A.chrom_block_off[c] = off;
         off += (long long) ((chrom_len[c] + WS_TILE - 1) / WS_TILE) * n_tracks;
@@ -216,7 +214,7 @@ int wtamd_synth_count(uint64_t seed, int n_chrom, const int32_t *chrom_len, int 
     if (rc != WTAMD_OK) return rc;
     hipLaunchKernelGGL(ws_count_kernel, dim3((unsigned) (nb < (1ll << 22) ? nb : (1ll << 22))), dim3(WS_BLOCK), 0, (hipStream_t) stream, A,
                        (long long *) counts, nb);
-    if (hipGetLastError() != hipSuccess) return wt_fail_ext(WTAMD_ERR_HIP, "wtamd_synth_count: launch failed");
+    if (hipGetLastError() != hipSuccess) return wt_fail(WTAMD_ERR_HIP, "wtamd_synth_count: launch failed");
     return WTAMD_OK;
 }
 
@@ -229,7 +227,7 @@ int wtamd_synth_fill(uint64_t seed, int n_chrom, const int32_t *chrom_len, int n
     if (rc != WTAMD_OK) return rc;
     hipLaunchKernelGGL(ws_fill_kernel, dim3((unsigned) (nb < (1ll << 22) ? nb : (1ll << 22))), dim3(WS_BLOCK), 0, (hipStream_t) stream, A,
                        (const long long *) block_off, start, finish, value, nb);
-    if (hipGetLastError() != hipSuccess) return wt_fail_ext(WTAMD_ERR_HIP, "wtamd_synth_fill: launch failed");
+    if (hipGetLastError() != hipSuccess) return wt_fail(WTAMD_ERR_HIP, "wtamd_synth_fill: launch failed");
     return WTAMD_OK;
 }
 
