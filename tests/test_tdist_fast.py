@@ -1,7 +1,9 @@
 """The t-test's tail as the DEVICE computes it (csrc/wt_core.h wt_tdist_2Q_fast: one asymptotic series for
 lgamma(a + 1/2) - lgamma(a), the continued fraction by a division-free forward recurrence) against the form the oracle and
 the emulator use (modified Lentz + lgamma, oracle/wt_oracle.c) and against scipy, over the (t, nu) plane.  Compiled for the
-host from the same source (tests/emu); the device differs only in its libm."""
+host from the same source (tests/emu); the device differs only in its libm -- pinned by tests/test_ttest_tail_plane.py, which holds
+the kernels' own results (every route to wt_ttest_tail, constructed (t, nu)) to the bound of test_fast_tail_against_mpmath below:
+the device's error was that of the host-compiled form to 0.001 of the bound (profiles/ttest_tail_plane.txt)."""
 import ctypes as C
 import math
 
