@@ -392,6 +392,37 @@ int wtamd_pipe_set_map(struct wtamd_pipe *p, const wtamd_map_chain *chains /* n_
  * WTAMD_MAP_CHAIN_MAX: message and exit(1). */
 WiggleIterator *wtamd_MapIterator(WiggleIterator *child, int map_op, double param);
 
+/* Coverage and union of OVERLAPPING intervals on device (csrc/wt_cover.hip): what turns reads and regions (BED, BAM,
+ * bigBed: the reference's readers with `overlaps = true`) into the non-overlapping tracks everything else here consumes.
+ * Input in the layout of wtamd_runs_map: start / finish (and value, f32 or f64) are DEVICE arrays, seg_off / o_seg_off HOST
+ * arrays of n_seg + 1 offsets; inside a segment the intervals are sorted by start (finishes in any order) and
+ * start < finish -- anything else: WTAMD_ERR_ARG, nothing written.  The o_* arrays are DEVICE memory of `capacity` runs;
+ * when the result does not fit: WTAMD_ERR_CAPACITY with *n_out = the count needed.  Synchronous on `stream`.
+ *
+ * wtamd_runs_coverage -- the reference's CoverageWiggleIterator (src/unaryOps.c:303-375, the `coverage` command): per
+ * segment, with B the sorted distinct starts and finishes, one run [B[k], B[k+1]) of value #(start <= B[k]) -
+ * #(finish <= B[k]) wherever that is > 0.  Runs are not merged where the depth stays the same (touching intervals give two
+ * runs of equal value), input values are ignored, depth 0 emits nothing; at most 2n - 1 runs from n intervals; values are
+ * exact integers in f64.  ONE DEVIATION: when its child runs dry the reference reads the exhausted child's stale start
+ * (:333-334) and emits one run with start == finish per stream; this library does not emit it.  Scratch: 12 bytes per 64 bp
+ * of a segment's extent plus 16 bytes per interval, in passes of at most WTAMD_COVER_SCRATCH_MB (default 256) MiB of the
+ * former; a larger segment is cut at positions.
+ *
+ * wtamd_runs_union -- the reference's UnionWiggleIterator (:60-92, what NonOverlappingWiggleIterator puts in front of every
+ * Multiplexer child): an interval joins the current group while group.finish > start (touching intervals do not merge); the
+ * group has the first member's start and value (carried bit for bit, widened to f64) and the largest finish; at most n runs. */
+int wtamd_runs_coverage(int64_t n_seg, const int64_t *seg_off, const int32_t *start, const int32_t *finish,
+                        int64_t capacity, int32_t *o_start, int32_t *o_finish, double *o_value,
+                        int64_t *o_seg_off, int64_t *n_out, void *stream);
+int wtamd_runs_union(int64_t n_seg, const int64_t *seg_off, const int32_t *start, const int32_t *finish,
+                     const void *value, int value_is_f64, int64_t capacity,
+                     int32_t *o_start, int32_t *o_finish, double *o_value,
+                     int64_t *o_seg_off, int64_t *n_out, void *stream);
+/* wtamd_runs_coverage of ONE segment held in HOST arrays, result in HOST arrays (what wtamd_CoverageIterator calls per
+ * chromosome): device memory, copies and the call on the null stream. */
+int wtamd_runs_coverage_host(int64_t n, const int32_t *start, const int32_t *finish, int64_t capacity, int32_t *o_start,
+                             int32_t *o_finish, double *o_value, int64_t *n_out);
+
 /* Run compression on device (reference CompressionWiggleIterator, unaryOps.c:235-253, which the
  * default writer applies, wigWriter.c:263-267): adjacent runs of one chromosome merge while
  * start == previous finish and (both NaN or |value - value of the group's first run| < 1e-6).
@@ -593,6 +624,23 @@ void wtamd_pool_trim(void);
 WiggleIterator *wtamd_ArrayReader(int n_chrom, const char *const *chrom_names, const int64_t *seg_off,
                                   const int32_t *start, const int32_t *finish, const float *value,
                                   double default_value);
+/* The same arrays holding OVERLAPPING intervals: sorted by start only (finishes in any order), `overlaps` set -- what the
+ * reference's BED / BAM / bigBed readers deliver.  seek() delivers the intervals that intersect the window, clipped, from a
+ * filtered copy.  A Multiplexer puts the union in front of it (NonOverlappingWiggleIterator); wtamd_CoverageIterator turns
+ * it into a depth track.  Bulk-capable. */
+WiggleIterator *wtamd_OverlappingArrayReader(int n_chrom, const char *const *chrom_names, const int64_t *seg_off,
+                                             const int32_t *start, const int32_t *finish, const float *value,
+                                             double default_value);
+/* The reference's CoverageWiggleIterator (src/unaryOps.c:303-375; the parser's `coverage`) on the device: returns `child`
+ * itself when it does not overlap; otherwise drains it one chromosome at a time (in blocks when it is bulk-capable, by pop()
+ * otherwise), computes the chromosome's depth track with wtamd_runs_coverage and serves it as a bulk source -- the
+ * library's Multiplexer takes it in blocks, wtamd_iterator_next_block hands out the rest of the current chromosome, a
+ * foreign pop() walks it run by run.  default_value 0, `overlaps` false; seek() seeks the child, then recomputes.  Values
+ * are doubles for pop() / next_block and float32 inside Multiplexer blocks: exact up to a depth of 2^24.  WITHOUT the
+ * reference's run of start == finish at the last distinct start of every stream (it reads the exhausted child's stale
+ * start, :333-334).  WTAMD_NO_DEVICE_COVERAGE=1 (or a build of the drop-in layer without the HIP units) computes the same
+ * list with a host sweep.  A child that is not sorted by start: message and exit(1). */
+WiggleIterator *wtamd_CoverageIterator(WiggleIterator *child);
 /* BigWig reader: the role of the reference's BigWiggleReader (src/bigWiggleReader.c:147-151) on this
  * library's own section decoder -- chromosomes in strcmp order, 1-based starts, box != 0: intervals
  * cut at the reference reader's 10 000-bp stretch edges (what `write_bg` parity needs); one producer
@@ -631,7 +679,8 @@ WiggleIterator *wtamd_MaxIntegrator(WiggleIterator *wi);
 WiggleIterator *wtamd_MinIntegrator(WiggleIterator *wi);
 WiggleIterator *wtamd_SpanIntegrator(WiggleIterator *wi);
 /* Consumer door, for reducers built by this library: the runs from the iterator's current element
- * to the end of the batch it belongs to, as arrays valid until the next call on `wi`.  Returns the
+ * to the end of the batch it belongs to (a wtamd_CoverageIterator: to the end of its chromosome), as arrays valid until
+ * the next call on `wi`.  Returns the
  * number of runs (0 and wi->done at the end).  Mixes freely with pop(). */
 int64_t wtamd_iterator_next_block(WiggleIterator *wi, const char **chrom, const int32_t **start,
                                   const int32_t **finish, const double **value);

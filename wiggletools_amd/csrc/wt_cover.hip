@@ -1,0 +1,132 @@
+// wt_cover.hip -- coverage and union of overlapping intervals on the device: the reference's CoverageWiggleIterator
+// (src/unaryOps.c:303-375, the `coverage` command) and UnionWiggleIterator (:60-92) over whole run lists in HBM.  The passes
+// and the two doors are written once in csrc/wt_cover.h (which tests/cover_emu.cpp also compiles for the CPU); this unit
+// gives every pass its kernel and the doors their launcher.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <cstdlib>
+#include <string>
+#include <vector>
+
+#include "wt_host.h"
+#include "wt_cover.h"
+
+namespace {
+
+template <int K>
+__global__ void __launch_bounds__(WCV_BLOCK) wt_cover_kernel(WcvArgs a) {
+    __shared__ WcvLds lds;
+    wcv_run_block(K, a, (long long) blockIdx.x, &lds);
+}
+
+struct HipLauncher {
+    hipStream_t s;
+    void *alloc(size_t bytes) {
+        void *p = nullptr;
+        return hipMalloc(&p, bytes) == hipSuccess ? p : nullptr;
+    }
+    void release(void *p) { (void) hipFree(p); }
+    bool zero(void *p, size_t bytes) { return hipMemsetAsync(p, 0, bytes, s) == hipSuccess; }
+    bool to_host(void *h, const void *d, size_t bytes) {
+        return hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+    }
+    bool to_device(void *d, const void *h, size_t bytes) {
+        // (the host tables are reused by the caller: the copy has left them when this returns)
+        return hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+    }
+    template <int K> bool launch(long long blocks, const WcvArgs &a) {
+        if (blocks <= 0) return true;
+        if (blocks > 0x7fffffffll) return false;
+        hipLaunchKernelGGL(wt_cover_kernel<K>, dim3((unsigned) blocks), dim3(WCV_BLOCK), 0, s, a);
+        return hipGetLastError() == hipSuccess;
+    }
+    bool run(int kernel, long long blocks, const WcvArgs &a) {
+        switch (kernel) {
+        case WCV_K_PRE: return launch<WCV_K_PRE>(blocks, a);
+        case WCV_K_MARK: return launch<WCV_K_MARK>(blocks, a);
+        case WCV_K_RANK: return launch<WCV_K_RANK>(blocks, a);
+        case WCV_K_SCAN_SUM: return launch<WCV_K_SCAN_SUM>(blocks, a);
+        case WCV_K_DELTA: return launch<WCV_K_DELTA>(blocks, a);
+        case WCV_K_DSUM: return launch<WCV_K_DSUM>(blocks, a);
+        case WCV_K_DEPTH: return launch<WCV_K_DEPTH>(blocks, a);
+        case WCV_K_EMIT: return launch<WCV_K_EMIT>(blocks, a);
+        case WCV_K_SEGOFF: return launch<WCV_K_SEGOFF>(blocks, a);
+        case WCV_K_UKEY: return launch<WCV_K_UKEY>(blocks, a);
+        case WCV_K_SCAN_MAX: return launch<WCV_K_SCAN_MAX>(blocks, a);
+        case WCV_K_UPM: return launch<WCV_K_UPM>(blocks, a);
+        case WCV_K_UHEAD: return launch<WCV_K_UHEAD>(blocks, a);
+        case WCV_K_UEMIT: return launch<WCV_K_UEMIT>(blocks, a);
+        default: return false;
+        }
+    }
+};
+
+int wcv_report(const char *door, int rc, const char *why) {
+    if (rc == 0) return WTAMD_OK;
+    if (rc == 3) return wt_fail(WTAMD_ERR_CAPACITY, std::string(door) + ": the output arrays are too small (*n_out holds the count needed)");
+    if (rc == 1) return wt_fail(WTAMD_ERR_ARG, std::string(door) + ": " + why);
+    const hipError_t e = hipGetLastError();
+    return wt_fail(WTAMD_ERR_HIP, std::string(door) + ": " + why + " (" + hipGetErrorString(e) + ")");
+}
+
+long long wcv_budget() {
+    const char *e = getenv("WTAMD_COVER_SCRATCH_MB");
+    const long long mb = e && atoll(e) > 0 ? atoll(e) : 256;
+    return mb << 20;
+}
+
+}  // namespace
+
+extern "C" {
+
+int wtamd_runs_coverage(int64_t n_seg, const int64_t *seg_off, const int32_t *start, const int32_t *finish, int64_t capacity,
+                        int32_t *o_start, int32_t *o_finish, double *o_value, int64_t *o_seg_off, int64_t *n_out, void *stream) {
+    HipLauncher l{(hipStream_t) stream};
+    const char *why = "";
+    const int rc = wcv_coverage(l, (long long) n_seg, seg_off, start, finish, (long long) capacity, o_start, o_finish, o_value, o_seg_off,
+                                n_out, wcv_budget(), &why);
+    return wcv_report("wtamd_runs_coverage", rc, why);
+}
+
+int wtamd_runs_union(int64_t n_seg, const int64_t *seg_off, const int32_t *start, const int32_t *finish, const void *value,
+                     int value_is_f64, int64_t capacity, int32_t *o_start, int32_t *o_finish, double *o_value, int64_t *o_seg_off,
+                     int64_t *n_out, void *stream) {
+    HipLauncher l{(hipStream_t) stream};
+    const char *why = "";
+    const int rc = wcv_union(l, (long long) n_seg, seg_off, start, finish, value, value_is_f64, (long long) capacity, o_start, o_finish,
+                             o_value, o_seg_off, n_out, &why);
+    return wcv_report("wtamd_runs_union", rc, why);
+}
+
+// One segment in HOST memory in, its depth track in HOST memory out (what wtamd_CoverageIterator calls per chromosome).
+int wtamd_runs_coverage_host(int64_t n, const int32_t *start, const int32_t *finish, int64_t capacity, int32_t *o_start,
+                             int32_t *o_finish, double *o_value, int64_t *n_out) {
+    if (n < 0 || !n_out || (n > 0 && (!start || !finish))) return wt_fail(WTAMD_ERR_ARG, "wtamd_runs_coverage_host: bad argument");
+    *n_out = 0;
+    if (n == 0) return WTAMD_OK;
+    const int64_t cap = 2 * n - 1;
+    int32_t *d_in = nullptr, *d_out = nullptr;
+    double *d_val = nullptr;
+    WT_HIP(hipMalloc(&d_in, sizeof(int32_t) * 2 * (size_t) n));
+    struct Free { void *p; ~Free() { (void) hipFree(p); } } f1{d_in};
+    WT_HIP(hipMalloc(&d_out, sizeof(int32_t) * 2 * (size_t) cap));
+    Free f2{d_out};
+    WT_HIP(hipMalloc(&d_val, sizeof(double) * (size_t) cap));
+    Free f3{d_val};
+    WT_HIP(hipMemcpy(d_in, start, sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice));
+    WT_HIP(hipMemcpy(d_in + n, finish, sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice));
+    const int64_t seg[2] = {0, n};
+    int64_t oseg[2] = {0, 0};
+    const int rc = wtamd_runs_coverage(1, seg, d_in, d_in + n, cap, d_out, d_out + cap, d_val, oseg, n_out, nullptr);
+    if (rc != WTAMD_OK) return rc;
+    if (*n_out > capacity) return wt_fail(WTAMD_ERR_CAPACITY, "wtamd_runs_coverage_host: the output arrays are too small (*n_out holds the count needed)");
+    if (*n_out > 0) {
+        WT_HIP(hipMemcpy(o_start, d_out, sizeof(int32_t) * (size_t) *n_out, hipMemcpyDeviceToHost));
+        WT_HIP(hipMemcpy(o_finish, d_out + cap, sizeof(int32_t) * (size_t) *n_out, hipMemcpyDeviceToHost));
+        WT_HIP(hipMemcpy(o_value, d_val, sizeof(double) * (size_t) *n_out, hipMemcpyDeviceToHost));
+    }
+    return WTAMD_OK;
+}
+
+}  // extern "C"

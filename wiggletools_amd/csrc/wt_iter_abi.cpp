@@ -31,7 +31,8 @@
 //
 // There is no CPU evaluation path here: every run, aligned tile or reduced value comes
 // from the HIP kernels.  If no GPU is present the first engine call fails and the
-// process exits(1) with the engine's message.
+// process exits(1) with the engine's message.  (One exception, csrc/wt_abi_cover.h: the depth track of
+// wtamd_CoverageIterator comes from a host sweep when the device door is not linked in or switched off.)
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -126,6 +127,7 @@ void wt_bulk_pop(WiggleIterator *wi) {
 #include "wt_abi_feeder.h"
 #include "wt_abi_reduce.h"
 #include "wt_abi_readers.h"
+#include "wt_abi_cover.h"
 #include "wt_abi_bwdev.h"
 #include "wt_abi_ops.h"
 #include "wt_abi_integrators.h"
@@ -450,9 +452,57 @@ WiggleIterator *wtamd_BufferedArrayReader(int n_chrom, const char *const *chrom_
     return wi;
 }
 
+// The same arrays as wtamd_ArrayReader, but OVERLAPPING: sorted by start only, `overlaps` set (what the reference's BED /
+// BAM / bigBed readers deliver).  newMultiplexer puts the union in front of it, wtamd_CoverageIterator turns it into depth.
+WiggleIterator *wtamd_OverlappingArrayReader(int n_chrom, const char *const *chrom_names, const int64_t *seg_off,
+                                             const int32_t *start, const int32_t *finish, const float *value,
+                                             double default_value) {
+    OvlReader *a = new (calloc(1, sizeof(OvlReader))) OvlReader();
+    a->hdr.peek = &ovl_peek;
+    a->hdr.advance = &ovl_advance;
+    a->hdr.stable = false;                     // (a seek replaces the arrays by the window's copy)
+    a->n_chrom = n_chrom;
+    a->names = (char **) calloc((size_t) (n_chrom > 0 ? n_chrom : 1), sizeof(char *));
+    a->seg_off = (int64_t *) calloc((size_t) n_chrom + 1, sizeof(int64_t));
+    for (int c = 0; c < n_chrom; c++) a->names[c] = strdup(chrom_names[c]);
+    for (int c = 0; c <= n_chrom; c++) a->seg_off[c] = seg_off[c];
+    a->start = start; a->finish = finish; a->value = value;
+    a->cs = start; a->cf = finish; a->cv = value;
+    a->c = -1; a->j = 0; a->end = 0;
+    WiggleIterator *wi = (WiggleIterator *) calloc(1, sizeof(WiggleIterator));
+    wi->data = a;
+    wi->pop = &wt_bulk_pop;
+    wi->seek = &ovl_seek;
+    wi->value = 1;
+    wi->overlaps = 1;
+    wi->default_value = default_value;
+    a->settle(wi);
+    return wi;
+}
+
+// CoverageWiggleIterator (unaryOps.c:367-375) on the device door: the child itself when it does not overlap
+WiggleIterator *wtamd_CoverageIterator(WiggleIterator *child) {
+    if (!child->overlaps) return child;
+    CovIter *c = new (calloc(1, sizeof(CovIter))) CovIter();
+    c->hdr.peek = &cov_peek;
+    c->hdr.advance = &cov_advance;
+    c->hdr.stable = false;                     // the run list is replaced chromosome by chromosome
+    c->child = child;
+    WiggleIterator *wi = (WiggleIterator *) calloc(1, sizeof(WiggleIterator));
+    wi->data = c;
+    wi->pop = &wt_bulk_pop;
+    wi->seek = &cov_seek;
+    wi->value = 1;
+    wi->overlaps = 0;
+    wi->default_value = 0;                     // :372
+    cov_settle(c, wi);                         // a fresh iterator already holds its first element (wiggleIterator.c:32)
+    return wi;
+}
+
 int64_t wtamd_iterator_next_block(WiggleIterator *wi, const char **chrom, const int32_t **start,
                                   const int32_t **finish, const double **value) {
-    if (!wi || wi->pop != &red_pop) return -1;          // reducers of this library only
+    if (cov_is(wi)) return cov_next_block(wi, chrom, start, finish, value);     // a coverage iterator: to the end of its chromosome
+    if (!wi || wi->pop != &red_pop) return -1;          // otherwise reducers of this library only
     RedState *R = red_state(wi);
     if (R->block_done) red_pop(wi);                     // the previous block emptied its batch: fetch the next
     if (wi->done) return 0;

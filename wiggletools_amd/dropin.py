@@ -84,6 +84,25 @@ def buffered_array_reader(chrom_names, seg_off, start_ptr, finish_ptr, value_ptr
     return L.wtamd_BufferedArrayReader(len(chrom_names), names, so.ctypes.data, start_ptr, finish_ptr, value_ptr, float(default_value))
 
 
+def overlapping_array_reader(chrom_names, seg_off, start_ptr, finish_ptr, value_ptr, default_value=0.0):
+    """wtamd_OverlappingArrayReader: wtamd_ArrayReader's arguments, intervals sorted by start only, `overlaps` set."""
+    L = _bind()
+    L.wtamd_OverlappingArrayReader.restype = C.c_void_p
+    L.wtamd_OverlappingArrayReader.argtypes = L.wtamd_ArrayReader.argtypes
+    names = (C.c_char_p * len(chrom_names))(*[n.encode() for n in chrom_names])
+    so = np.ascontiguousarray(seg_off, np.int64)
+    return L.wtamd_OverlappingArrayReader(len(chrom_names), names, so.ctypes.data, start_ptr, finish_ptr, value_ptr, float(default_value))
+
+
+def coverage_iterator(child):
+    """wtamd_CoverageIterator: the reference's `coverage` around an overlapping child (the child itself when it does not
+    overlap); a bulk source for multiplexer() / reducer(), readable with drain_blocks() and drain_pops()."""
+    L = _bind()
+    L.wtamd_CoverageIterator.restype = C.c_void_p
+    L.wtamd_CoverageIterator.argtypes = [C.c_void_p]
+    return L.wtamd_CoverageIterator(child)
+
+
 def bigwig_reader(path, box=True):
     """wtamd_BigWiggleReader: the reference's BigWiggleReader role (bigWiggleReader.c:147-151), bulk-capable."""
     return _bind().wtamd_BigWiggleReader(path.encode(), int(box))
@@ -127,14 +146,14 @@ def seek(wi, chrom, start, finish):
 
 
 def drain_blocks(wi, on_block=None):
-    """Consumes a reducer through the block door; returns (runs, covered bp)."""
+    """Consumes a reducer (or a coverage iterator) through the block door; returns (runs, covered bp)."""
     L = _bind()
     chrom, s, f, v = C.c_char_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
     runs = bp = 0
     while True:
         n = L.wtamd_iterator_next_block(wi, C.byref(chrom), C.byref(s), C.byref(f), C.byref(v))
         if n < 0:
-            raise _lib.WtamdError("wtamd_iterator_next_block: not a reducer of this library")
+            raise _lib.WtamdError("wtamd_iterator_next_block: neither a reducer nor a coverage iterator of this library")
         if n == 0:
             return runs, bp
         runs += n

@@ -61,6 +61,53 @@ def map_runlists(rl: RunLists, op, param=0.0):
     return RunLists(rl.n_chrom, rl.n_tracks, oseg, os_[:m].cpu().numpy(), of[:m].cpu().numpy(), ov[:m].cpu().numpy(), d)
 
 
+def _overlap_door(rl, union, capacity=None):
+    """wtamd_runs_coverage / wtamd_runs_union over every segment of `rl`; returns (rc, runs needed, RunLists or None)."""
+    import torch
+    dev = torch.device("cuda", torch.cuda.current_device())
+    n = int(rl.seg_off[-1])
+    n_seg = rl.n_chrom * rl.n_tracks
+    cap = (n if union else max(2 * n - 1, 0)) if capacity is None else int(capacity)
+    seg = np.ascontiguousarray(rl.seg_off, np.int64)
+    s = torch.from_numpy(np.ascontiguousarray(rl.start, np.int32)).to(dev)
+    f = torch.from_numpy(np.ascontiguousarray(rl.finish, np.int32)).to(dev)
+    os_ = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+    of = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+    ov = torch.empty(max(cap, 1), dtype=torch.float64, device=dev)
+    oseg = np.zeros(n_seg + 1, np.int64)
+    n_out = C.c_int64()
+    L = _lib.lib()
+    if union:
+        v = torch.from_numpy(np.ascontiguousarray(rl.value)).to(dev)
+        rc = L.wtamd_runs_union(n_seg, seg.ctypes.data, s.data_ptr(), f.data_ptr(), v.data_ptr(), 1 if rl.value.dtype == np.float64 else 0,
+                                cap, os_.data_ptr(), of.data_ptr(), ov.data_ptr(), oseg.ctypes.data, C.byref(n_out), None)
+    else:
+        rc = L.wtamd_runs_coverage(n_seg, seg.ctypes.data, s.data_ptr(), f.data_ptr(), cap, os_.data_ptr(), of.data_ptr(), ov.data_ptr(),
+                                   oseg.ctypes.data, C.byref(n_out), None)
+    if rc != 0:
+        return rc, n_out.value, None
+    m = n_out.value
+    d = rl.defaults if union else np.zeros(rl.n_tracks, np.float64)
+    return 0, m, RunLists(rl.n_chrom, rl.n_tracks, oseg, os_[:m].cpu().numpy(), of[:m].cpu().numpy(), ov[:m].cpu().numpy(), d, rl.chrom_names)
+
+
+def coverage_runlists(rl: RunLists):
+    """The reference's `coverage` (CoverageWiggleIterator, unaryOps.c:303-375) over every track of `rl`, whose intervals may
+    overlap (each segment sorted by start), on device (wtamd_runs_coverage): the depth tracks as a new RunLists, f64 values,
+    defaults 0.  Without the reference's one run of start == finish per stream (include/wiggletools_amd.h)."""
+    rc, _, out = _overlap_door(rl, False)
+    _lib.check(rc)
+    return out
+
+
+def union_runlists(rl: RunLists):
+    """The reference's UnionWiggleIterator (unaryOps.c:60-92) over every track of `rl` on device (wtamd_runs_union):
+    overlapping intervals merged into groups with the first member's start and value (f64) and the largest finish."""
+    rc, _, out = _overlap_door(rl, True)
+    _lib.check(rc)
+    return out
+
+
 class TrackSet:
     """N tracks resident in HBM (wtamd_trackset)."""
 
