@@ -423,6 +423,42 @@ int wtamd_runs_union(int64_t n_seg, const int64_t *seg_off, const int32_t *start
 int wtamd_runs_coverage_host(int64_t n, const int32_t *start, const int32_t *finish, int64_t capacity, int32_t *o_start,
                              int32_t *o_finish, double *o_value, int64_t *n_out);
 
+/* Region operators on device (csrc/wt_region.hip): the reference's OverlapWiggleIterator, NoverlapWiggleIterator,
+ * TrimWiggleIterator and NearestWiggleIterator (src/unaryOps.c:437-639; the parser's `overlaps`, `noverlaps`, `trim`,
+ * `nearest`, commandParser.c:813-819) over whole run lists: a source restricted to, or measured against, a mask.  Source and
+ * mask come in the layout of wtamd_runs_map with the SAME n_seg, segment g of one pairing with segment g of the other:
+ * start / finish (and the source's value, f32 or f64) are DEVICE arrays, the seg_off arrays HOST arrays of n_seg + 1
+ * offsets; inside a segment both are sorted by start with start < finish, and either may overlap itself, except the source
+ * of a trim.  Per segment, with S the source, M the mask, G = the union of M as wtamd_runs_union defines it (touching
+ * intervals stay apart), lo(i) = the first group with G.finish > S.start[i], hi(i) = the first group with
+ * G.start >= S.finish[i]:
+ *   OVERLAPS    run i iff hi(i) > lo(i); start, finish and value carried unchanged
+ *   NOVERLAPS   run i iff hi(i) <= lo(i) (every run where the mask is empty)
+ *   TRIM        for g in [lo(i), hi(i)), in that order: [max(S.start, G.start[g]), min(S.finish, G.finish[g])) with the
+ *               value of run i; at most n + |G| - 1 runs per segment; two touching mask intervals cut a run in two
+ *   NEAREST     exactly the source's runs; with k = #(M.start <= S.start[i]) over the RAW mask the value is the smaller of
+ *               S.start[i] - M.finish[k-1] + 1 (if k > 0) and M.start[k] - S.finish[i] + 1 (if k < m), in int32
+ *               arithmetic, 0 where that is negative, NaN where there is no candidate.  The reference's quirks are kept:
+ *               the + 1; the "previous" mask is the one that started last, not the one that ends last; an earlier mask
+ *               that encloses the run is not seen.
+ * Values are carried bit for bit and widened to f64.  WTAMD_ERR_ARG with nothing written: an unknown op, a segment that is
+ * not sorted by start or holds start >= finish (either side), a TRIM source with start[i] < finish[i-1] (the reference's
+ * output then depends on the order of its pops and loses intersections; wtamd_RegionIterator serves that case by the
+ * reference's protocol on the host).  The o_* arrays are DEVICE memory of `capacity` runs, o_seg_off a HOST array; when the
+ * result does not fit: WTAMD_ERR_CAPACITY with *n_out = the count needed, nothing written.  Synchronous on `stream`.
+ * Scratch: 8 bytes per mask interval (the union), 8 bytes per 1024 source runs. */
+enum wtamd_region_op { WTAMD_REGION_OVERLAPS = 0, WTAMD_REGION_NOVERLAPS = 1, WTAMD_REGION_TRIM = 2, WTAMD_REGION_NEAREST = 3 };
+int wtamd_runs_region(int op, int64_t n_seg,
+                      const int64_t *seg_off, const int32_t *start, const int32_t *finish, const void *value, int value_is_f64,
+                      const int64_t *m_seg_off, const int32_t *m_start, const int32_t *m_finish,
+                      int64_t capacity, int32_t *o_start, int32_t *o_finish, double *o_value,
+                      int64_t *o_seg_off, int64_t *n_out, void *stream);
+/* wtamd_runs_region of ONE segment pair held in HOST arrays, result in HOST arrays (what wtamd_RegionIterator calls per
+ * chromosome): device memory, copies and the call on the null stream. */
+int wtamd_runs_region_host(int op, int64_t n, const int32_t *start, const int32_t *finish, const double *value,
+                           int64_t m, const int32_t *m_start, const int32_t *m_finish,
+                           int64_t capacity, int32_t *o_start, int32_t *o_finish, double *o_value, int64_t *n_out);
+
 /* Run compression on device (reference CompressionWiggleIterator, unaryOps.c:235-253, which the
  * default writer applies, wigWriter.c:263-267): adjacent runs of one chromosome merge while
  * start == previous finish and (both NaN or |value - value of the group's first run| < 1e-6).
@@ -641,6 +677,17 @@ WiggleIterator *wtamd_OverlappingArrayReader(int n_chrom, const char *const *chr
  * start, :333-334).  WTAMD_NO_DEVICE_COVERAGE=1 (or a build of the drop-in layer without the HIP units) computes the same
  * list with a host sweep.  A child that is not sorted by start: message and exit(1). */
 WiggleIterator *wtamd_CoverageIterator(WiggleIterator *child);
+/* The reference's OverlapWiggleIterator / NoverlapWiggleIterator / TrimWiggleIterator / NearestWiggleIterator
+ * (src/unaryOps.c:437-639) as one constructor; op is a wtamd_region_op (anything else: message and exit(1)).  Drains source
+ * and mask one chromosome at a time (in blocks where the child is bulk-capable, by pop() otherwise), pairing chromosomes by
+ * name in strcmp order as the reference does, computes the chromosome's result with wtamd_runs_region and serves it as a
+ * bulk source: the library's Multiplexer takes it in blocks, wtamd_iterator_next_block hands out the rest of the current
+ * chromosome, a foreign pop() walks it run by run.  default_value and `overlaps` are the source's; seek() seeks both
+ * children, then recomputes.  Values are doubles for pop() / next_block and float32 inside Multiplexer blocks, where a
+ * `nearest` distance above 2^24 is rounded.  A TRIM whose source overlaps itself is served by the reference's own
+ * per-interval protocol on the host.  WTAMD_NO_DEVICE_REGION=1 (or a build of the drop-in layer without the HIP units)
+ * computes the same lists with a host sweep.  A child that is not sorted by start: message and exit(1). */
+WiggleIterator *wtamd_RegionIterator(int op, WiggleIterator *source, WiggleIterator *mask);
 /* BigWig reader: the role of the reference's BigWiggleReader (src/bigWiggleReader.c:147-151) on this
  * library's own section decoder -- chromosomes in strcmp order, 1-based starts, box != 0: intervals
  * cut at the reference reader's 10 000-bp stretch edges (what `write_bg` parity needs); one producer

@@ -105,6 +105,8 @@ add(body(8, "#### `wm_map_kernel` / `wm_compact_kernel` — the `map`-able unary
 add("")
 add(body(13, "#### Operator chains inside the pipeline (`wt_map_chain_async`, `wtamd_pipe_set_map`)"))
 add("")
+add(new("0485_region"))
+add("")
 add("### 4.9 Pipeline kernels and the BigWig kernels")
 add("")
 add(body(11, "#### `wt_gather_kernel`, `wt_export_kernel` (`csrc/wt_pipe.hip`)"))

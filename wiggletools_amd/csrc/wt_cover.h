@@ -507,8 +507,10 @@ WCV_DEV void wcv_uemit_block(const WcvArgs &a, long long block, WcvLds *lds) {
                 if (heads < a.capacity) {
                     a.o_start[heads] = a.start[i];
                     // bit for bit: a NaN keeps its payload, -0.0 its sign (f32 widens exactly)
-                    if (a.value_is_f64) ((unsigned long long *) a.o_value)[heads] = ((const unsigned long long *) a.value)[i];
-                    else a.o_value[heads] = (double) ((const float *) a.value)[i];
+                    if (a.o_value) {                                                    // (NULL: coordinates only, csrc/wt_region.h)
+                        if (a.value_is_f64) ((unsigned long long *) a.o_value)[heads] = ((const unsigned long long *) a.value)[i];
+                        else a.o_value[heads] = (double) ((const float *) a.value)[i];
+                    }
                 }
                 heads++;
             }
@@ -701,8 +703,9 @@ static int wcv_union(L &l, long long n_seg, const int64_t *seg_off, const int32_
     const long long n = n_seg ? (long long) (seg_off[n_seg] - seg_off[0]) : 0;
     *n_out = 0;
     if (n == 0) { for (long long g = 0; g <= n_seg; g++) o_seg_off[g] = 0; return 0; }
-    if (!start || !finish || !value || seg_off[0] != 0 || n_seg >= (1ll << 31)) { *why = "bad argument"; return 1; }
-    if ((capacity > 0 && (!o_start || !o_finish || !o_value))) { *why = "bad argument"; return 1; }
+    // (value and o_value both NULL: the groups' coordinates alone, what csrc/wt_region.h asks for a mask)
+    if (!start || !finish || (!value && o_value) || seg_off[0] != 0 || n_seg >= (1ll << 31)) { *why = "bad argument"; return 1; }
+    if ((capacity > 0 && (!o_start || !o_finish || (!o_value && value)))) { *why = "bad argument"; return 1; }
     WcvScope<L> sc(l);
     WcvArgs a = {};
     a.start = start; a.finish = finish; a.value = value; a.value_is_f64 = value_is_f64; a.n_seg = n_seg; a.capacity = capacity;

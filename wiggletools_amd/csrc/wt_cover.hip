@@ -78,6 +78,12 @@ long long wcv_budget() {
 
 }  // namespace
 
+// one pass of wt_cover.h on a stream, for the other units that use them (csrc/wt_region.hip: the union of a mask, the scan)
+bool wt_cover_run(void *stream, int kernel, long long blocks, const WcvArgs &a) {
+    HipLauncher l{(hipStream_t) stream};
+    return l.run(kernel, blocks, a);
+}
+
 extern "C" {
 
 int wtamd_runs_coverage(int64_t n_seg, const int64_t *seg_off, const int32_t *start, const int32_t *finish, int64_t capacity,

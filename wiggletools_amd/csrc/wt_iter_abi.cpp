@@ -32,7 +32,8 @@
 // There is no CPU evaluation path here: every run, aligned tile or reduced value comes
 // from the HIP kernels.  If no GPU is present the first engine call fails and the
 // process exits(1) with the engine's message.  (One exception, csrc/wt_abi_cover.h: the depth track of
-// wtamd_CoverageIterator comes from a host sweep when the device door is not linked in or switched off.)
+// wtamd_CoverageIterator comes from a host sweep when the device door is not linked in or switched off; so does the run list
+// of wtamd_RegionIterator, csrc/wt_abi_region.h.)
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -128,6 +129,7 @@ void wt_bulk_pop(WiggleIterator *wi) {
 #include "wt_abi_reduce.h"
 #include "wt_abi_readers.h"
 #include "wt_abi_cover.h"
+#include "wt_abi_region.h"
 #include "wt_abi_bwdev.h"
 #include "wt_abi_ops.h"
 #include "wt_abi_integrators.h"
@@ -499,9 +501,34 @@ WiggleIterator *wtamd_CoverageIterator(WiggleIterator *child) {
     return wi;
 }
 
+// Overlap / Noverlap / Trim / NearestWiggleIterator (unaryOps.c:437-639) on the device door
+WiggleIterator *wtamd_RegionIterator(int op, WiggleIterator *source, WiggleIterator *mask) {
+    if (op < WTAMD_REGION_OVERLAPS || op > WTAMD_REGION_NEAREST) {
+        fprintf(stderr, "wiggletools_amd: wtamd_RegionIterator: unknown operator %d\n", op);
+        exit(1);
+    }
+    RegIter *c = new (calloc(1, sizeof(RegIter))) RegIter();
+    c->hdr.peek = &reg_peek;
+    c->hdr.advance = &reg_advance;
+    c->hdr.stable = false;                     // the run list is replaced chromosome by chromosome
+    c->op = op;
+    c->source = source;
+    c->mask = mask;
+    WiggleIterator *wi = (WiggleIterator *) calloc(1, sizeof(WiggleIterator));
+    wi->data = c;
+    wi->pop = &wt_bulk_pop;
+    wi->seek = &reg_seek;
+    wi->value = 1;
+    wi->overlaps = source->overlaps;           // :478
+    wi->default_value = source->default_value;
+    reg_settle(c, wi);                         // a fresh iterator already holds its first element (wiggleIterator.c:32)
+    return wi;
+}
+
 int64_t wtamd_iterator_next_block(WiggleIterator *wi, const char **chrom, const int32_t **start,
                                   const int32_t **finish, const double **value) {
     if (cov_is(wi)) return cov_next_block(wi, chrom, start, finish, value);     // a coverage iterator: to the end of its chromosome
+    if (reg_is(wi)) return reg_next_block(wi, chrom, start, finish, value);     // a region iterator likewise
     if (!wi || wi->pop != &red_pop) return -1;          // otherwise reducers of this library only
     RedState *R = red_state(wi);
     if (R->block_done) red_pop(wi);                     // the previous block emptied its batch: fetch the next

@@ -103,6 +103,16 @@ def coverage_iterator(child):
     return L.wtamd_CoverageIterator(child)
 
 
+def region_iterator(op, source, mask):
+    """wtamd_RegionIterator: the reference's `overlaps`, `noverlaps`, `trim` or `nearest` (engine.REGION_OPS) of `source`
+    against `mask`; a bulk source for multiplexer() / reducer(), readable with drain_blocks() and drain_pops()."""
+    from .engine import REGION_OPS
+    L = _bind()
+    L.wtamd_RegionIterator.restype = C.c_void_p
+    L.wtamd_RegionIterator.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
+    return L.wtamd_RegionIterator(REGION_OPS[op] if isinstance(op, str) else int(op), source, mask)
+
+
 def bigwig_reader(path, box=True):
     """wtamd_BigWiggleReader: the reference's BigWiggleReader role (bigWiggleReader.c:147-151), bulk-capable."""
     return _bind().wtamd_BigWiggleReader(path.encode(), int(box))

@@ -108,6 +108,50 @@ def union_runlists(rl: RunLists):
     return out
 
 
+REGION_OPS = {"overlaps": 0, "noverlaps": 1, "trim": 2, "nearest": 3}      # WTAMD_REGION_*
+
+
+def _region_door(op, source, mask, capacity=None):
+    """wtamd_runs_region over every segment pair of `source` and `mask`; op: a name of REGION_OPS or a raw code.  Returns
+    (rc, runs needed, RunLists or None)."""
+    import torch
+    dev = torch.device("cuda", torch.cuda.current_device())
+    op = REGION_OPS[op] if isinstance(op, str) else int(op)
+    n_seg = source.n_chrom * source.n_tracks
+    if mask.n_chrom * mask.n_tracks != n_seg:
+        raise ValueError("region: source and mask must have the same number of segments")
+    n, m = int(source.seg_off[-1]), int(mask.seg_off[-1])
+    cap = (n + m if op == REGION_OPS["trim"] else n) if capacity is None else int(capacity)
+    seg, mseg = np.ascontiguousarray(source.seg_off, np.int64), np.ascontiguousarray(mask.seg_off, np.int64)
+    s = torch.from_numpy(np.ascontiguousarray(source.start, np.int32)).to(dev)
+    f = torch.from_numpy(np.ascontiguousarray(source.finish, np.int32)).to(dev)
+    v = torch.from_numpy(np.ascontiguousarray(source.value)).to(dev)
+    ms = torch.from_numpy(np.ascontiguousarray(mask.start, np.int32)).to(dev)
+    mf = torch.from_numpy(np.ascontiguousarray(mask.finish, np.int32)).to(dev)
+    os_ = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+    of = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+    ov = torch.empty(max(cap, 1), dtype=torch.float64, device=dev)
+    oseg = np.zeros(n_seg + 1, np.int64)
+    n_out = C.c_int64()
+    rc = _lib.lib().wtamd_runs_region(op, n_seg, seg.ctypes.data, s.data_ptr(), f.data_ptr(), v.data_ptr(),
+                                      1 if source.value.dtype == np.float64 else 0, mseg.ctypes.data, ms.data_ptr(), mf.data_ptr(), cap,
+                                      os_.data_ptr(), of.data_ptr(), ov.data_ptr(), oseg.ctypes.data, C.byref(n_out), None)
+    if rc != 0:
+        return rc, n_out.value, None
+    k = n_out.value
+    return 0, k, RunLists(source.n_chrom, source.n_tracks, oseg, os_[:k].cpu().numpy(), of[:k].cpu().numpy(), ov[:k].cpu().numpy(),
+                          source.defaults, source.chrom_names)
+
+
+def region_runlists(op, source: RunLists, mask: RunLists):
+    """The reference's `overlaps`, `noverlaps`, `trim` or `nearest` (unaryOps.c:437-639) of every segment of `source`
+    against the segment of `mask` at the same place, on device (wtamd_runs_region): a new RunLists with f64 values and the
+    source's defaults.  A trim source must not overlap itself (include/wiggletools_amd.h)."""
+    rc, _, out = _region_door(op, source, mask)
+    _lib.check(rc)
+    return out
+
+
 class TrackSet:
     """N tracks resident in HBM (wtamd_trackset)."""
 
