@@ -637,7 +637,8 @@ int64_t wtamd_pipe_bw_redone(const wtamd_pipe *);
 /* Pinned (page-locked, DMA-able) host memory for bulk sources. */
 void *wtamd_host_alloc(size_t bytes);
 void wtamd_host_free(void *);
-/* The process-wide pools behind the pipes: page-locked staging (also wtamd_host_alloc; WTAMD_PINNED_POOL_MB) and
+/* The process-wide pools behind the pipes, the track sets (their window tables, counters and staging) and the scratch of
+ * the host entry points: page-locked memory (also wtamd_host_alloc; WTAMD_PINNED_POOL_MB) and
  * device buffers (WTAMD_DEVICE_POOL_MB).  out[0..2]: pinned buffers of 1 MB and more that had to be page-locked afresh
  * so far (count, bytes) and the bytes resting in the pool now; out[3..5]: the same for device buffers (hipMalloc).  A
  * second run of the same job in a process should add no misses. */

@@ -1969,32 +1969,8 @@ WT_DEV void wt_index_apply(const WtParams &P, WtIndexCursor &c, long long g, int
         for (long long m = m_hi + 1; m <= c.nw; m++) P.widx[(size_t) (c.rowbase + m) * N + c.i] = (uint32_t) (jr + 1);
 }
 
-// first x in [lo, hi) with fin[x] >= b (hi if none), starting from a guess g in [lo, hi)
-WT_DEV long long wt_lane_lower_bound(const int32_t *fin, long long lo, long long hi, long long g, long long b) {
-    if (lo >= hi) return lo;
-    if ((long long) fin[g] >= b) {
-        hi = g;
-        for (long long d = 1;; d <<= 1) {
-            const long long q = hi - d;
-            if (q < lo) break;
-            if ((long long) fin[q] < b) { lo = q + 1; break; }
-            hi = q;
-        }
-    } else {
-        lo = g + 1;
-        for (long long d = 1;; d <<= 1) {
-            const long long q = lo + d - 1;
-            if (q >= hi) break;
-            if ((long long) fin[q] >= b) { hi = q; break; }
-            lo = q + 1;
-        }
-    }
-    while (lo < hi) {
-        const long long mid = (lo + hi) >> 1;
-        if ((long long) fin[mid] < b) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
+// (the lane search of the window index, wt_lane_lower_bound among it: a header of its own that a host program can include)
+#include "wt_isearch.h"
 
 #include "wt_delta.h"
 #include "wt_walk.h"

@@ -7,6 +7,7 @@
 //   wt_index_kernel     window index (widx): contiguous span of input runs per block, 4 per lane
 //   wt_index_coarse_kernel / wt_index_search_kernel   the same index by search
 //   wt_extents_kernel   first start / last finish per (chrom, track) segment
+//   wt_win_chrom_kernel / wt_clear_kernel   the window -> chromosome table; what a launch clears first
 //   wt_validate_kernel  input contract (sorted, non-overlapping, positive length)
 #include <hip/hip_runtime.h>
 
@@ -25,6 +26,7 @@
 #include "wt_plan.h"
 #include "wt_kernels.h"
 #include "wt_devscope.h"
+#include "wt_pool.h"
 
 // ---------------------------------------------------------------------------
 // kernels
@@ -110,12 +112,14 @@ __global__ void __launch_bounds__(256) wt_index_kernel(const WtParams P, long lo
 // in the track's finish[] (wt_index_apply's claims, restated), so nothing obliges the kernel to read every
 // finish: at a mean run of 16 bp the scan above reads 256 entries (1 KB) per boundary and stays near
 // 3.3 TB/s whatever its loads look like (1, 2 or 4 vectors in flight, long or short spans per block).
-//   coarse  every 64th row of every track by a plain binary search over the track's whole segment
-//           (one lane each; ~1 % of the boundaries, the upper levels of the search stay in L2);
+//   coarse  every 64th row of every track by an interpolation search over the track's whole segment
+//           (one lane each; ~1 % of the boundaries);
 //   fine    a wave owns the 64 rows between two coarse rows of ONE track: each lane interpolates its boundary
-//           between the two coarse answers and gallops / bisects from the guess -- a few probes, almost all
-//           inside one or two 128-byte lines; the 16 waves of a workgroup (16 neighbouring tracks, same
-//           rows) exchange through LDS so that a row is written as one 64-byte piece.
+//           between the two coarse answers, corrects the guess twice by the bracket's density (the linear guess is
+//           ~90 runs off at a mean run of 16 bp, the corrected one a few) and gallops / bisects from there
+//           (wt_isearch.h) -- 5 dependent probes on average where the gallop alone took 11, almost all inside one
+//           or two 128-byte lines; the 16 waves of a workgroup (16 neighbouring tracks, same rows) exchange
+//           through LDS so that a row is written as one 64-byte piece.
 // (A first version found the bracket with a cooperative 64-ary search per wave: 17.7 ms against the scan's
 // 22-27 -- its 64 probes per step were 64 cache lines per step.)  Same result as the scan by construction;
 // WTAMD_INDEX=scan selects the scan, WTAMD_INDEX_CHECK=1 runs both and compares (tests).
@@ -133,26 +137,50 @@ __device__ __forceinline__ int wt_index_row_chrom(const WtParams &P, long long r
     return lo;
 }
 
-// coarse[strip][track]: the index entry of row strip * 64
+// the chromosome of an index row, its boundary and the track's finish[] segment.  One chromosome (wave-uniform branch): no
+// search, and the tables' entries are loads at a uniform address
+struct WtIndexRow { int ch; long long b, s0, n; };
+__device__ __forceinline__ WtIndexRow wt_index_row(const WtParams &P, long long row, int i) {
+    WtIndexRow r;
+    r.ch = P.n_chrom == 1 ? 0 : wt_index_row_chrom(P, row);
+    const long long m = row - (P.c_first_win[r.ch] + r.ch);
+    const long long seg = (long long) r.ch * P.n_tracks + i;
+    r.s0 = P.seg_off[seg];
+    r.n = P.seg_off[seg + 1] - r.s0;
+    r.b = (long long) P.cbase[r.ch] + (m << P.logW);
+    return r;
+}
+
+// coarse[strip][track]: the index entry of row strip * 64.  An interpolation search (wt_isearch.h) from the segment's end
+// points: the density is the segment's, the first guess linear between its first and last finish -- 2 + up to ~8 dependent
+// probes where the plain binary search took log2(n) = 21 to 24, on a grid far too small to hide them.
 __global__ void __launch_bounds__(256) wt_index_coarse_kernel(const WtParams P, long long n_strips, uint32_t *coarse) {
     const long long t = (long long) blockIdx.x * 256 + threadIdx.x;
     const int N = P.n_tracks;
     if (t >= n_strips * N) return;
     const long long strip = t / N;
     const int i = (int) (t - strip * N);
-    const long long row = strip * WT_ISEARCH_ROWS;
-    const int ch = wt_index_row_chrom(P, row);
-    const long long m = row - (P.c_first_win[ch] + ch);
-    const long long seg = (long long) ch * N + i;
-    const long long s0 = P.seg_off[seg], n = P.seg_off[seg + 1] - s0;
-    const long long b = (long long) P.cbase[ch] + (m << P.logW);
-    coarse[t] = (uint32_t) wt_lane_lower_bound(P.finish + s0, 0, n, n >> 1, b);
+    const WtIndexRow r = wt_index_row(P, strip * WT_ISEARCH_ROWS, i);
+    const int32_t *fin = P.finish + r.s0;
+    long long g = r.n >> 1;
+    float density = 0.0f;
+    if (r.n > 1) {
+        const long long f0 = fin[0], f1 = fin[r.n - 1];
+        if (f1 > f0) {
+            density = (float) (r.n - 1) / (float) (f1 - f0);
+            const float guess = fminf(fmaxf((float) (r.b - f0) * density, 0.0f), (float) (r.n - 1));
+            g = (long long) guess;
+            if (g > r.n - 1) g = r.n - 1;
+        }
+    }
+    coarse[t] = (uint32_t) wt_interp_lower_bound(WtFinArray{fin}, 0, r.n, g, r.b, density);
 }
 
 __global__ void __launch_bounds__(WT_ISEARCH_ROWS * WT_ISEARCH_TRACKS) wt_index_search_kernel(const WtParams P, long long n_rows, long long n_strips,
                                                                                               const uint32_t *coarse) {
     __shared__ uint32_t out[WT_ISEARCH_ROWS][WT_ISEARCH_TRACKS + 1];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // (told to the compiler: what hangs on the track alone is scalar)
     const int N = P.n_tracks;
     const long long strip = blockIdx.x;
     const long long r0 = strip * WT_ISEARCH_ROWS;
@@ -160,23 +188,27 @@ __global__ void __launch_bounds__(WT_ISEARCH_ROWS * WT_ISEARCH_TRACKS) wt_index_
     if (i < N) {                                    // (wave-uniform)
         long long row = r0 + lane;
         if (row > n_rows - 1) row = n_rows - 1;     // the last strip: duplicates of the last row, not stored
-        const int ch = wt_index_row_chrom(P, row);
-        const long long m = row - (P.c_first_win[ch] + ch);
-        const long long seg = (long long) ch * N + i;
-        const long long s0 = P.seg_off[seg], n = P.seg_off[seg + 1] - s0;
-        const long long b = (long long) P.cbase[ch] + (m << P.logW);
-        const int32_t *fin = P.finish + s0;
-        // the bracket: the coarse answers of this strip's and the next strip's first rows, where they belong
-        // to the lane's chromosome (a strip may straddle a chromosome edge)
-        const int ch_first = __shfl(ch, 0);
+        const WtIndexRow r = wt_index_row(P, row, i);
+        const int32_t *fin = P.finish + r.s0;
+        // the bracket: the coarse answers of this strip's and the next strip's first rows (wave-uniform loads), where they
+        // belong to the lane's chromosome (a strip may straddle a chromosome edge)
         const bool have_next = strip + 1 < n_strips;
-        const int ch_next = have_next ? wt_index_row_chrom(P, r0 + WT_ISEARCH_ROWS) : -1;
-        const bool real_a = ch == ch_first, real_b = ch == ch_next;
-        const long long A = real_a ? (long long) coarse[strip * N + i] : 0;
-        const long long B = real_b ? (long long) coarse[(strip + 1) * N + i] : n;
+        const long long cA = (long long) coarse[strip * N + i];
+        const long long cB = have_next ? (long long) coarse[(strip + 1) * N + i] : 0;
+        bool real_a = true, real_b = have_next;
+        if (P.n_chrom != 1) {
+            const int ch_first = __shfl(r.ch, 0);
+            const int ch_next = have_next ? wt_index_row_chrom(P, r0 + WT_ISEARCH_ROWS) : -1;
+            real_a = r.ch == ch_first; real_b = r.ch == ch_next;
+        }
+        const long long A = real_a ? cA : 0;
+        const long long B = real_b ? cB : r.n;
         long long g = (real_a && real_b) ? A + (((B - A) * lane) >> 6) : (A + B) >> 1;
         if (g > B - 1) g = B - 1;
-        out[lane][wave] = (uint32_t) wt_lane_lower_bound(fin, A, B, g, b);
+        // both ends real: the bracket's B - A runs lie between two boundaries 64 windows apart -- its density moves the guess
+        // (wt_interp_lower_bound) before the gallop; at a chromosome's edge the gallop runs alone, as it always did
+        const float density = (real_a && real_b) ? (float) (B - A) / (float) ((long long) WT_ISEARCH_ROWS << P.logW) : 0.0f;
+        out[lane][wave] = (uint32_t) wt_interp_lower_bound(WtFinArray{fin}, A, B, g, r.b, density);
     }
     __syncthreads();
     const int orow = tid / WT_ISEARCH_TRACKS, ocol = tid % WT_ISEARCH_TRACKS;
@@ -199,6 +231,30 @@ __global__ void __launch_bounds__(256) wt_extents_kernel(const int64_t *seg_off,
     const long long lo = seg_off[s], hi = seg_off[s + 1];
     first_start[s] = hi > lo ? start[lo] : 0;
     last_finish[s] = hi > lo ? finish[hi - 1] : 0;
+}
+
+// win_chrom[k]: the chromosome of window k, from c_first_win[] (strictly increasing: every chromosome has a window).  The
+// table is filled where it is read: a track set of several chromosomes uploads n_chrom entries instead of n_windows.
+__global__ void __launch_bounds__(256) wt_win_chrom_kernel(const int64_t *c_first_win, int n_chrom, long long n_windows, int32_t *win_chrom) {
+    const long long k = (long long) blockIdx.x * 256 + threadIdx.x;
+    if (k >= n_windows) return;
+    int lo = 0;
+    for (int hi = n_chrom; hi - lo > 1;) {
+        const int mid = (lo + hi) >> 1;
+        if (c_first_win[mid] <= k) lo = mid; else hi = mid;
+    }
+    win_chrom[k] = lo;
+}
+
+// What every launch clears first -- the counters, the per-chromosome run offsets, the look-back words -- in ONE kernel: as
+// three hipMemsetAsync calls they stood between the index and the reducing kernel for 30 us of every launch (13 us of fill
+// kernels, the rest the gaps between them; profiles/fresh_step.md).
+__global__ void __launch_bounds__(256) wt_clear_kernel(unsigned long long *counters, int n_counters, int64_t *chrom_run_off, int n_cro,
+                                                        unsigned long long *status, long long n_status) {
+    const long long t = (long long) blockIdx.x * 256 + threadIdx.x, stride = (long long) gridDim.x * 256;
+    for (long long q = t; q < n_status; q += stride) status[q] = 0ull;
+    for (long long q = t; q < n_counters; q += stride) counters[q] = 0ull;
+    for (long long q = t; q < n_cro; q += stride) chrom_run_off[q] = 0;
 }
 
 // Input contract check (sorted, non-overlapping, positive-length runs inside every (chrom, track)
@@ -233,23 +289,34 @@ int wt_fail(int code, const std::string &msg) {
     return code;
 }
 
+// Device tables come from the device pool and return to it (wt_pool.h).  The pool waits for nothing, so a table that is
+// outgrown waits for the device before it returns: once per growth (*quiet: the caller's growth has waited already).
 template <class T>
-static hipError_t wt_grow(T **p, int64_t *cap, int64_t need) {
+static hipError_t wt_grow(T **p, int64_t *cap, int64_t need, bool *quiet) {
     if (*cap >= need && *p) return hipSuccess;
     int64_t c = *cap * 2;
     if (c < need) c = need;
     if (c < 1) c = 1;
-    (void) hipFree(*p);
+    if (*p) {
+        if (!*quiet) {
+            const hipError_t eq = wt_pool_quiesce();
+            if (eq != hipSuccess) return eq;
+            *quiet = true;
+        }
+        (void) wt_dev_free(*p);
+    }
     *p = nullptr; *cap = 0;
-    const hipError_t e = hipMalloc((void **) p, sizeof(T) * (size_t) c);
+    const hipError_t e = wt_dev_alloc(p, sizeof(T) * (size_t) c);
     if (e == hipSuccess) *cap = c;
     return e;
 }
 
+// (the caller has waited for the device: wtamd_trackset_destroy)
 static void wt_free_windows(WtWindows &w) {
-    (void) hipFree(w.d_tabs);          // (d_cbase, d_cnwin, d_chi, d_cfirst, d_win_chrom point into it)
-    (void) hipFree(w.d_widx); (void) hipFree(w.d_cidx); (void) hipFree(w.d_status); (void) hipFree(w.d_bad_list); (void) hipFree(w.d_bad_goff);
-    if (w.h_tab) (void) hipHostFree(w.h_tab);
+    (void) wt_dev_free(w.d_tabs);          // (d_cbase, d_cnwin, d_chi, d_cfirst, d_win_chrom point into it)
+    (void) wt_dev_free(w.d_widx); (void) wt_dev_free(w.d_cidx); (void) wt_dev_free(w.d_status); (void) wt_dev_free(w.d_bad_list); (void) wt_dev_free(w.d_bad_goff);
+    if (w.h_tab) wt_host_free(w.h_tab);
+    if (w.ev_tab) (void) hipEventDestroy(w.ev_tab);
     w = WtWindows();
 }
 
@@ -348,15 +415,15 @@ extern "C++" int wt_trackset_common(const wtamd_tracks *t, wtamd_trackset *ts) {
     hipDeviceProp_t prop;
     WT_HIP(hipGetDeviceProperties(&prop, ts->device));
     ts->num_cu = prop.multiProcessorCount;
-    WT_HIP(hipMalloc(&ts->d_seg_off, sizeof(int64_t) * (n_seg + 1)));
+    WT_HIP(wt_dev_alloc(&ts->d_seg_off, sizeof(int64_t) * (n_seg + 1)));
     WT_HIP(hipMemcpy(ts->d_seg_off, ts->seg_off.data(), sizeof(int64_t) * (n_seg + 1), hipMemcpyHostToDevice));
-    WT_HIP(hipMalloc(&ts->d_defaults, sizeof(double) * t->n_tracks));
+    WT_HIP(wt_dev_alloc(&ts->d_defaults, sizeof(double) * t->n_tracks));
     WT_HIP(hipMemcpy(ts->d_defaults, ts->defaults.data(), sizeof(double) * t->n_tracks, hipMemcpyHostToDevice));
-    WT_HIP(hipMalloc(&ts->d_counters, sizeof(unsigned long long) * WT_CTR_N));
-    WT_HIP(hipHostMalloc(&ts->h_counters, sizeof(unsigned long long) * WT_CTR_N));
-    WT_HIP(hipHostMalloc(&ts->h_debug, sizeof(unsigned long long) * 16));
+    WT_HIP(wt_dev_alloc(&ts->d_counters, sizeof(unsigned long long) * WT_CTR_N));
+    WT_HIP(wt_host_alloc((void **) &ts->h_counters, sizeof(unsigned long long) * WT_CTR_N));
+    WT_HIP(wt_host_alloc((void **) &ts->h_debug, sizeof(unsigned long long) * 16));
     memset(ts->h_debug, 0, sizeof(unsigned long long) * 16);
-    WT_HIP(hipMalloc(&ts->d_chrom_run_off, sizeof(int64_t) * (t->n_chrom + 1)));
+    WT_HIP(wt_dev_alloc(&ts->d_chrom_run_off, sizeof(int64_t) * (t->n_chrom + 1)));
     WT_HIP(hipEventCreate(&ts->ev_i0));
     WT_HIP(hipEventCreate(&ts->ev_i1));
     WT_HIP(hipEventCreate(&ts->ev_r0));
@@ -376,21 +443,23 @@ extern "C++" int wt_check_extents(wtamd_trackset *ts) {
     return WTAMD_OK;
 }
 
-// Device-side (first start, last finish) of every (chrom, track) segment into the host copies.
-static int wt_refresh_extents_device(wtamd_trackset *ts) {
+// Device-side (first start, last finish) of every (chrom, track) segment into the host copies: one kernel on the caller's
+// stream, one asynchronous copy of both arrays into the track set's pinned buffer, one synchronisation of that stream.
+static int wt_refresh_extents_device(wtamd_trackset *ts, hipStream_t s) {
     const int64_t n_seg = (int64_t) ts->n_chrom * ts->n_tracks;
     ts->first_start.assign(n_seg, 0);
     ts->last_finish.assign(n_seg, 0);
     if (n_seg > 0 && ts->n_intervals > 0) {
-        int32_t *d_fs = nullptr, *d_lf = nullptr;
-        WtDevScope scope;
-        WT_HIP(scope.alloc(&d_fs, sizeof(int32_t) * n_seg));
-        WT_HIP(scope.alloc(&d_lf, sizeof(int32_t) * n_seg));
-        hipLaunchKernelGGL(wt_extents_kernel, dim3((unsigned) ((n_seg + 255) / 256)), dim3(256), 0, 0,
-                           ts->d_seg_off, ts->d_start, ts->d_finish, (long long) n_seg, d_fs, d_lf);
+        const size_t bytes = sizeof(int32_t) * 2 * (size_t) n_seg;
+        if (!ts->d_extents) WT_HIP(wt_dev_alloc(&ts->d_extents, bytes));
+        if (!ts->h_extents) WT_HIP(wt_host_alloc((void **) &ts->h_extents, bytes));
+        hipLaunchKernelGGL(wt_extents_kernel, dim3((unsigned) ((n_seg + 255) / 256)), dim3(256), 0, s,
+                           ts->d_seg_off, ts->d_start, ts->d_finish, (long long) n_seg, ts->d_extents, ts->d_extents + n_seg);
         WT_HIP(hipGetLastError());
-        WT_HIP(hipMemcpy(ts->first_start.data(), d_fs, sizeof(int32_t) * n_seg, hipMemcpyDeviceToHost));
-        WT_HIP(hipMemcpy(ts->last_finish.data(), d_lf, sizeof(int32_t) * n_seg, hipMemcpyDeviceToHost));
+        WT_HIP(hipMemcpyAsync(ts->h_extents, ts->d_extents, bytes, hipMemcpyDeviceToHost, s));
+        WT_HIP(hipStreamSynchronize(s));
+        ts->first_start.assign(ts->h_extents, ts->h_extents + n_seg);
+        ts->last_finish.assign(ts->h_extents + n_seg, ts->h_extents + 2 * n_seg);
     }
     return WTAMD_OK;
 }
@@ -438,7 +507,7 @@ static int wt_create_device_impl(const wtamd_tracks *t, wtamd_trackset *ts) {
     ts->d_start = const_cast<int32_t *>(t->start);
     ts->d_finish = const_cast<int32_t *>(t->finish);
     ts->d_value = const_cast<void *>(t->value);
-    rc = wt_refresh_extents_device(ts);
+    rc = wt_refresh_extents_device(ts, nullptr);
     if (rc != WTAMD_OK) return rc;
     return wt_check_extents(ts);
 }
@@ -454,11 +523,18 @@ int wtamd_trackset_create_device(const wtamd_tracks *t, wtamd_trackset **out) {
 
 void wtamd_trackset_destroy(wtamd_trackset *ts) {
     if (!ts) return;
+    // The pools' rule (wt_pool.h): a buffer returns only after the device has finished with it.  A launch of this track set may
+    // be in flight on any stream (wtamd_reduce without n_runs returns at once), and the first hipFree used to wait for it: the
+    // wait is explicit now, once, before the first buffer goes back.
+    (void) wt_pool_quiesce();
     if (ts->owns) { (void) hipFree(ts->d_start); (void) hipFree(ts->d_finish); (void) hipFree(ts->d_value); }
-    (void) hipFree(ts->d_seg_off); (void) hipFree(ts->d_defaults); (void) hipFree(ts->d_counters); (void) hipFree(ts->d_chrom_run_off); (void) hipFree(ts->d_gscratch); (void) hipFree(ts->d_mwu_table);
+    (void) wt_dev_free(ts->d_seg_off); (void) wt_dev_free(ts->d_defaults); (void) wt_dev_free(ts->d_counters); (void) wt_dev_free(ts->d_chrom_run_off);
+    (void) wt_dev_free(ts->d_extents);
+    (void) hipFree(ts->d_gscratch); (void) hipFree(ts->d_mwu_table);
     for (double *q : ts->mwu_retired) (void) hipFree(q);
-    if (ts->h_counters) (void) hipHostFree(ts->h_counters);
-    if (ts->h_debug) (void) hipHostFree(ts->h_debug);
+    if (ts->h_counters) wt_host_free(ts->h_counters);
+    if (ts->h_debug) wt_host_free(ts->h_debug);
+    if (ts->h_extents) wt_host_free(ts->h_extents);
     for (auto &kv : ts->windows) wt_free_windows(kv.second);
     if (ts->ev_i0) (void) hipEventDestroy(ts->ev_i0);
     if (ts->ev_i1) (void) hipEventDestroy(ts->ev_i1);
@@ -490,64 +566,75 @@ int64_t wtamd_trackset_max_runs(const wtamd_trackset *ts) {
     return std::min<int64_t>(2 * ts->n_intervals, wt_span(ts));
 }
 
-// Window tables of width W for the track set's current data.  The device tables are kept and
-// reused (they only ever grow); a pipeline slot uploads them asynchronously on `s` from pinned
-// staging (its per-batch data is one chromosome: four scalars and an all-zero win_chrom[]).
+// Window tables of width W for the track set's current data.  The device tables come from the device pool, are kept and
+// reused (they only ever grow).  The per-chromosome tables travel in ONE asynchronous copy on `s` from this WtWindows' pinned
+// staging, packed as they lie at the head of d_tabs; win_chrom[] is filled on the device (all zeros for one chromosome: a
+// memset; wt_win_chrom_kernel otherwise).
 static int wt_get_windows(wtamd_trackset *ts, int W, WtWindows **out, hipStream_t s = nullptr) {
     WtWindows &w = ts->windows[W];
     *out = &w;
     if (w.tab_valid) return WTAMD_OK;
     wt_make_windows(ts->n_chrom, ts->n_tracks, ts->seg_off.data(), ts->first_start.data(), ts->last_finish.data(), W, w.tab,
                     ts->range_lo.empty() ? nullptr : ts->range_lo.data(),
-                    ts->range_hi.empty() ? nullptr : ts->range_hi.data());
+                    ts->range_hi.empty() ? nullptr : ts->range_hi.data(), false);
     w.indexed = false;
     const int64_t nc = ts->n_chrom > 0 ? ts->n_chrom : 1;
     const int64_t nwin = w.tab.n_windows > 0 ? w.tab.n_windows : 1;
     const int64_t nwidx = (w.tab.n_rows > 0 ? w.tab.n_rows : 1) * (int64_t) ts->n_tracks;
     // layout of the combined table allocation (8-byte aligned pieces)
     auto up8 = [](int64_t x) { return (x + 7) & ~(int64_t) 7; };
+    bool quiet = false;         // this growth has waited for the device (once, before the first table returns to the pool)
     if (w.cap_chrom < nc || w.cap_win < nwin || !w.d_tabs) {
-        // (growing: twice the old capacity at least, as wt_grow does -- a pipeline slot's batches creep up, and every hipFree waits for the device)
+        // (growing: twice the old capacity at least, as wt_grow does -- a pipeline slot's batches creep up)
         const int64_t cc = w.cap_chrom < nc ? std::max<int64_t>(nc, 2 * w.cap_chrom) : w.cap_chrom;
         const int64_t cw = w.cap_win < nwin ? std::max<int64_t>(nwin, 2 * w.cap_win) : w.cap_win;
         const int64_t o_cnwin = up8(4 * cc), o_chi = o_cnwin + up8(4 * cc), o_cfirst = o_chi + up8(4 * cc), o_win = o_cfirst + 8 * (cc + 1);
         const int64_t total = o_win + up8(4 * cw);
-        (void) hipFree(w.d_tabs);
+        if (w.d_tabs || w.d_status) { WT_HIP(wt_pool_quiesce()); quiet = true; }
+        (void) wt_dev_free(w.d_tabs);
         w.d_tabs = nullptr; w.cap_tabs = 0;
         w.d_cbase = w.d_cnwin = w.d_chi = w.d_win_chrom = nullptr; w.d_cfirst = nullptr;
-        if (w.cap_win < cw) { (void) hipFree(w.d_status); w.d_status = nullptr; }      // (cleared before every launch: its own allocation)
+        if (w.cap_win < cw) { (void) wt_dev_free(w.d_status); w.d_status = nullptr; }      // (cleared before every launch: its own allocation)
         w.cap_chrom = 0; w.cap_win = 0;
-        WT_HIP(hipMalloc((void **) &w.d_tabs, (size_t) total));
-        if (!w.d_status) WT_HIP(hipMalloc((void **) &w.d_status, sizeof(unsigned long long) * (size_t) cw));
+        WT_HIP(wt_dev_alloc(&w.d_tabs, (size_t) total));
+        if (!w.d_status) WT_HIP(wt_dev_alloc(&w.d_status, sizeof(unsigned long long) * (size_t) cw));
         w.cap_tabs = total;
         w.d_cbase = (int32_t *) w.d_tabs; w.d_cnwin = (int32_t *) (w.d_tabs + o_cnwin); w.d_chi = (int32_t *) (w.d_tabs + o_chi);
         w.d_cfirst = (int64_t *) (w.d_tabs + o_cfirst); w.d_win_chrom = (int32_t *) (w.d_tabs + o_win);
         w.cap_chrom = cc; w.cap_win = cw;
     }
-    WT_HIP(wt_grow(&w.d_widx, &w.cap_widx, nwidx));
-    WT_HIP(wt_grow(&w.d_cidx, &w.cap_cidx, ((w.tab.n_rows > 0 ? w.tab.n_rows : 1) + WT_ISEARCH_ROWS - 1) / WT_ISEARCH_ROWS * (int64_t) ts->n_tracks));
+    WT_HIP(wt_grow(&w.d_widx, &w.cap_widx, nwidx, &quiet));
+    WT_HIP(wt_grow(&w.d_cidx, &w.cap_cidx, ((w.tab.n_rows > 0 ? w.tab.n_rows : 1) + WT_ISEARCH_ROWS - 1) / WT_ISEARCH_ROWS * (int64_t) ts->n_tracks, &quiet));
     if (ts->n_chrom > 0) {
-        if (ts->pipe_mode) {
-            if (ts->n_chrom != 1) return wt_fail(WTAMD_ERR_INTERNAL, "pipeline slots hold one chromosome");
-            if (!w.h_tab) WT_HIP(hipHostMalloc((void **) &w.h_tab, 64, hipHostMallocDefault));
-            int32_t *h32 = (int32_t *) w.h_tab;
-            h32[0] = w.tab.cbase[0]; h32[1] = w.tab.c_nwin[0]; h32[2] = w.tab.c_hi[0];
-            w.h_tab[2] = w.tab.c_first_win[0]; w.h_tab[3] = w.tab.c_first_win[1];
-            WT_HIP(hipMemcpyAsync(w.d_cbase, h32 + 0, sizeof(int32_t), hipMemcpyHostToDevice, s));
-            WT_HIP(hipMemcpyAsync(w.d_cnwin, h32 + 1, sizeof(int32_t), hipMemcpyHostToDevice, s));
-            WT_HIP(hipMemcpyAsync(w.d_chi, h32 + 2, sizeof(int32_t), hipMemcpyHostToDevice, s));
-            WT_HIP(hipMemcpyAsync(w.d_cfirst, w.h_tab + 2, 2 * sizeof(int64_t), hipMemcpyHostToDevice, s));
-            WT_HIP(hipMemsetAsync(w.d_win_chrom, 0, sizeof(int32_t) * (size_t) nwin, s));
-        } else {
-            // one (blocking) copy of the five tables, packed as they lie on the device
-            const int64_t used = ((char *) w.d_win_chrom - w.d_tabs) + (int64_t) sizeof(int32_t) * std::max<int64_t>(w.tab.n_windows, 0);
-            std::vector<char> pack((size_t) used, 0);
-            memcpy(pack.data() + ((char *) w.d_cbase - w.d_tabs), w.tab.cbase.data(), sizeof(int32_t) * ts->n_chrom);
-            memcpy(pack.data() + ((char *) w.d_cnwin - w.d_tabs), w.tab.c_nwin.data(), sizeof(int32_t) * ts->n_chrom);
-            memcpy(pack.data() + ((char *) w.d_chi - w.d_tabs), w.tab.c_hi.data(), sizeof(int32_t) * ts->n_chrom);
-            memcpy(pack.data() + ((char *) w.d_cfirst - w.d_tabs), w.tab.c_first_win.data(), sizeof(int64_t) * (ts->n_chrom + 1));
-            if (w.tab.n_windows > 0) memcpy(pack.data() + ((char *) w.d_win_chrom - w.d_tabs), w.tab.win_chrom.data(), sizeof(int32_t) * w.tab.n_windows);
-            WT_HIP(hipMemcpy(w.d_tabs, pack.data(), (size_t) used, hipMemcpyHostToDevice));
+        if (ts->pipe_mode && ts->n_chrom != 1) return wt_fail(WTAMD_ERR_INTERNAL, "pipeline slots hold one chromosome");
+        // the staging is rewritten only after the event behind its previous upload has completed
+        if (!w.ev_tab) WT_HIP(hipEventCreateWithFlags(&w.ev_tab, hipEventDisableTiming));
+        if (w.tab_in_flight) { WT_HIP(hipEventSynchronize(w.ev_tab)); w.tab_in_flight = false; }
+        const int64_t head = (char *) w.d_win_chrom - w.d_tabs;         // the per-chromosome tables at this capacity
+        if (w.h_tab_bytes < head) {
+            if (w.h_tab) wt_host_free(w.h_tab);
+            w.h_tab = nullptr; w.h_tab_bytes = 0;
+            WT_HIP(wt_host_alloc((void **) &w.h_tab, (size_t) head));
+            w.h_tab_bytes = head;
+        }
+        const int64_t o_cfirst = (char *) w.d_cfirst - w.d_tabs;
+        const int64_t used = o_cfirst + (int64_t) sizeof(int64_t) * (ts->n_chrom + 1);
+        memset(w.h_tab, 0, (size_t) used);
+        memcpy(w.h_tab + ((char *) w.d_cbase - w.d_tabs), w.tab.cbase.data(), sizeof(int32_t) * ts->n_chrom);
+        memcpy(w.h_tab + ((char *) w.d_cnwin - w.d_tabs), w.tab.c_nwin.data(), sizeof(int32_t) * ts->n_chrom);
+        memcpy(w.h_tab + ((char *) w.d_chi - w.d_tabs), w.tab.c_hi.data(), sizeof(int32_t) * ts->n_chrom);
+        memcpy(w.h_tab + o_cfirst, w.tab.c_first_win.data(), sizeof(int64_t) * (ts->n_chrom + 1));
+        WT_HIP(hipMemcpyAsync(w.d_tabs, w.h_tab, (size_t) used, hipMemcpyHostToDevice, s));
+        WT_HIP(hipEventRecord(w.ev_tab, s));
+        w.tab_in_flight = true;
+        if (w.tab.n_windows > 0) {
+            if (ts->n_chrom == 1) {
+                WT_HIP(hipMemsetAsync(w.d_win_chrom, 0, sizeof(int32_t) * (size_t) w.tab.n_windows, s));
+            } else {
+                hipLaunchKernelGGL(wt_win_chrom_kernel, dim3((unsigned) ((w.tab.n_windows + 255) / 256)), dim3(256), 0, s,
+                                   (const int64_t *) w.d_cfirst, ts->n_chrom, (long long) w.tab.n_windows, w.d_win_chrom);
+                WT_HIP(hipGetLastError());
+            }
         }
     }
     w.tab_valid = true;
@@ -717,7 +804,7 @@ int wtamd_trackset_index(wtamd_trackset *ts, int op, void *stream) {
     if (!ts->owns && !ts->pipe_mode) {
         // zero-copy track set rewritten in place: its runs may start earlier / end later than
         // before, so the extents, their check and every width's window tables are rebuilt too
-        int rce = wt_refresh_extents_device(ts);
+        int rce = wt_refresh_extents_device(ts, (hipStream_t) stream);
         if (rce != WTAMD_OK) return rce;
         rce = wt_check_extents(ts);
         if (rce != WTAMD_OK) return rce;
@@ -892,8 +979,9 @@ static int wt_reduce_plan(wtamd_trackset *ts, const WtPlan &plan, int op, uint32
         const int64_t nwin = w->tab.n_windows > 0 ? w->tab.n_windows : 1;
         if (w->cap_bad < nwin) {
             int64_t c1 = w->cap_bad, c2 = w->cap_bad;
-            WT_HIP(wt_grow(&w->d_bad_list, &c1, nwin));
-            WT_HIP(wt_grow(&w->d_bad_goff, &c2, nwin * WT_BAD_SUB));
+            bool quiet = false;
+            WT_HIP(wt_grow(&w->d_bad_list, &c1, nwin, &quiet));
+            WT_HIP(wt_grow(&w->d_bad_goff, &c2, nwin * WT_BAD_SUB, &quiet));
             w->cap_bad = c1 < c2 / WT_BAD_SUB ? c1 : c2 / WT_BAD_SUB;
         }
         L.P.bad_list = w->d_bad_list;
@@ -901,10 +989,17 @@ static int wt_reduce_plan(wtamd_trackset *ts, const WtPlan &plan, int op, uint32
         wt_delta_defaults_params(ts->defaults.data(), ts->n_tracks, L.P);
     }
 
-    WT_HIP(hipMemsetAsync(ts->d_counters, 0, sizeof(unsigned long long) * WT_CTR_N, s));
-    WT_HIP(hipMemsetAsync(L.P.chrom_run_off, 0, sizeof(int64_t) * (ts->n_chrom + 1), s));
-    if (w->tab.n_windows > 0 && ts->n_intervals > 0) {
-        WT_HIP(hipMemsetAsync(w->d_status, 0, sizeof(unsigned long long) * w->tab.n_windows, s));
+    // the counters, the run offsets and (where a kernel follows) the look-back words, cleared by one kernel
+    const bool launches = w->tab.n_windows > 0 && ts->n_intervals > 0;
+    {
+        const long long n_status = launches ? (long long) w->tab.n_windows : 0;
+        const long long most = std::max<long long>(std::max<long long>(n_status, WT_CTR_N), ts->n_chrom + 1);
+        const unsigned blocks = (unsigned) std::min<long long>((most + 255) / 256, 1024);
+        hipLaunchKernelGGL(wt_clear_kernel, dim3(blocks), dim3(256), 0, s, ts->d_counters, (int) WT_CTR_N, L.P.chrom_run_off, ts->n_chrom + 1,
+                           w->d_status, n_status);
+        WT_HIP(hipGetLastError());
+    }
+    if (launches) {
         if (plan.delta) {
             // (tiles of 256 runs per wavefront and window, on average)
             static const int force_u = getenv("WTAMD_DELTA_U") ? atoi(getenv("WTAMD_DELTA_U")) : 0;

@@ -28,7 +28,9 @@ int wt_fail(int code, const std::string &msg);
 // Bounded wait: a kernel that does not finish is reported, never waited for forever.  A kernel that never finishes cannot
 // be cancelled and every later HIP call of this process (even hipFree) would block behind it: after WTAMD_TIMEOUT_S
 // (default 120) the process reports fatal(limit) and terminates.  query() is hipStreamQuery / hipEventQuery of what is waited
-// for (`call`, `what`: its name in the error message); the wait spins for nap_after_s, then sleeps nap_us between queries.
+// for (`call`, `what`: its name in the error message); the wait spins for nap_after_s, then sleeps between queries -- for 1/64
+// of the time already waited, nap_us at the most: a wait of a few milliseconds ends within 2 % of the kernel's end instead of
+// up to a whole nap_us quantum behind it, and a long one still leaves the core alone.
 template <class Query, class Fatal>
 static inline int wt_bounded_wait(Query query, const char *call, const char *what, double nap_after_s, int nap_us, Fatal fatal) {
     const double limit_s = getenv("WTAMD_TIMEOUT_S") ? atof(getenv("WTAMD_TIMEOUT_S")) : 120.0;
@@ -43,7 +45,10 @@ static inline int wt_bounded_wait(Query query, const char *call, const char *wha
             fflush(stderr);
             _exit(70);
         }
-        if (el > nap_after_s) std::this_thread::sleep_for(std::chrono::microseconds(nap_us));
+        if (el > nap_after_s) {
+            const double nap = el * (1e6 / 64.0);
+            std::this_thread::sleep_for(std::chrono::nanoseconds((long long) (1e3 * (nap < (double) nap_us ? nap : (double) nap_us))));
+        }
     }
 }
 

@@ -1,5 +1,5 @@
-// wt_pipe.hip -- the streaming pipeline's unit: the gather and export kernels, every wtamd_pipe_* entry and the pooled
-// allocators behind wtamd_host_* / wtamd_pool_* (overview: wt_pipe.h).  The kernels of a batch are the engine's and the side
+// wt_pipe.hip -- the streaming pipeline's unit: the gather and export kernels, every wtamd_pipe_* entry and
+// wtamd_host_* (overview: wt_pipe.h; the pools themselves and wtamd_pool_*: wt_pool.hip).  The kernels of a batch are the engine's and the side
 // units': this file stages, orders and ships.  Compiled only by hipcc --offload-arch=gfx950.
 #include <hip/hip_runtime.h>
 
@@ -1000,33 +1000,7 @@ void wtamd_host_free(void *q) {
     if (q) wt_host_free(q);
 }
 
-void wtamd_pool_trim(void) {
-    std::vector<void *> host, dev;
-    {
-        std::lock_guard<std::mutex> lk(g_pinned_pool.mu);
-        for (auto &kv : g_pinned_pool.free_list) { host.push_back(kv.second); g_pinned_pool.size_of.erase(kv.second); }
-        g_pinned_pool.free_list.clear();
-        g_pinned_pool.pooled = 0;
-    }
-    {
-        std::lock_guard<std::mutex> lk(g_dev_pool.mu);
-        for (auto &kv : g_dev_pool.free_list) { dev.push_back(kv.second); g_dev_pool.size_of.erase(kv.second); }
-        g_dev_pool.free_list.clear();
-        g_dev_pool.pooled = 0;
-    }
-    for (void *x : host) wt_pin_raw_free(x);
-    for (void *x : dev) (void) hipFree(x);
-}
-
-void wtamd_pool_stats(int64_t out[6]) {
-    if (!out) return;
-    {
-        std::lock_guard<std::mutex> lk(g_pinned_pool.mu);
-        out[0] = (int64_t) g_pinned_pool.misses; out[1] = (int64_t) g_pinned_pool.miss_bytes; out[2] = (int64_t) g_pinned_pool.pooled;
-    }
-    std::lock_guard<std::mutex> lk(g_dev_pool.mu);
-    out[3] = (int64_t) g_dev_pool.misses; out[4] = (int64_t) g_dev_pool.miss_bytes; out[5] = (int64_t) g_dev_pool.pooled;
-}
+// (wtamd_pool_trim / wtamd_pool_stats: wt_pool.hip, with the pools)
 
 int wtamd_pipe_get_stats(const wtamd_pipe *p, wtamd_pipe_stats *out) {
     if (!p || !out) return wt_fail(WTAMD_ERR_ARG, "NULL argument");

@@ -471,7 +471,7 @@ struct WtWindowTables {
 static inline void wt_make_windows(int n_chrom, int n_tracks, const int64_t *seg_off,
                                    const int32_t *first_start, const int32_t *last_finish, int W,
                                    WtWindowTables &t, const int32_t *range_lo = nullptr,
-                                   const int32_t *range_hi = nullptr) {
+                                   const int32_t *range_hi = nullptr, bool with_win_chrom = true) {
     t.cbase.assign(n_chrom, 0);
     t.c_nwin.assign(n_chrom, 1);
     t.c_hi.assign(n_chrom, INT32_MAX);
@@ -508,7 +508,8 @@ static inline void wt_make_windows(int n_chrom, int n_tracks, const int64_t *seg
         t.c_nwin[c] = (int32_t) nw;
         if (range_hi) t.c_hi[c] = range_hi[c];
         t.c_first_win[c + 1] = t.c_first_win[c] + nw;
-        for (int64_t m = 0; m < nw; m++) t.win_chrom.push_back(c);
+        // (the engine fills the device's win_chrom[] on the device and passes false: 30 000 entries for chromosome 1)
+        if (with_win_chrom) t.win_chrom.insert(t.win_chrom.end(), (size_t) nw, c);
     }
     t.n_windows = t.c_first_win[n_chrom];
     t.n_rows = t.n_windows + n_chrom;

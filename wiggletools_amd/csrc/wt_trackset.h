@@ -1,5 +1,6 @@
 // wt_trackset.h -- the engine's internal interface (wt_engine.hip): the track set, its window tables and the engine
-// functions the streaming pipeline (wt_pipe.hip) is built on.  Host side only.
+// functions the streaming pipeline (wt_pipe.hip) is built on.  Host side only.  Every device and pinned buffer named here
+// comes from the pools of wt_pool.h and returns to them (d_gscratch and the MWU tables excepted: hipMalloc / hipFree).
 #ifndef WT_TRACKSET_H_
 #define WT_TRACKSET_H_
 
@@ -23,7 +24,13 @@ struct WtWindows {
     // capacities of the device tables (entries); the tables are reused and only ever grow
     int64_t cap_chrom = 0, cap_win = 0, cap_widx = 0, cap_bad = 0, cap_cidx = 0;
     bool tab_valid = false;             // tab / device tables describe the track set's current data
-    int64_t *h_tab = nullptr;           // pinned staging of the per-chromosome tables (pipeline slots: asynchronous upload)
+    // Pinned staging of the per-chromosome tables, packed as they lie at the head of d_tabs: ONE asynchronous copy on the launch
+    // stream uploads them (win_chrom[] is filled on the device).  The staging is this WtWindows' own and is rewritten only after
+    // the event behind its previous upload has completed.
+    char *h_tab = nullptr;
+    int64_t h_tab_bytes = 0;
+    hipEvent_t ev_tab = nullptr;        // recorded behind every upload
+    bool tab_in_flight = false;         // an upload was enqueued since ev_tab was last waited for
     // round 6: cbase | cnwin | chi | cfirst | win_chrom live in ONE allocation (d_tabs) and travel in ONE copy -- a NEW track set's first
     // index paid five hipMallocs and five blocking copies for them, 0.1 ms of host time per chromosome of a resident pass
     char *d_tabs = nullptr;
@@ -47,6 +54,9 @@ struct wtamd_trackset {
     unsigned long long *h_counters = nullptr;   // pinned
     unsigned long long *h_debug = nullptr;      // pinned, device-visible (debug builds)
     int64_t *d_chrom_run_off = nullptr;         // scratch when the caller passes none
+    // zero-copy track sets: (first start | last finish) of every segment as the device reads them off the run lists, and the
+    // pinned buffer one asynchronous copy brings them to (wt_refresh_extents_device)
+    int32_t *d_extents = nullptr, *h_extents = nullptr;
     char *d_gscratch = nullptr;                 // median / MWU columns of very many tracks (grown on demand)
     size_t gscratch_bytes = 0;
     double *d_mwu_table = nullptr;              // MWUReduction's last step as a table (wt_mwu_make_table), for set sizes mwu_n1 / mwu_n2
