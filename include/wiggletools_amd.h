@@ -459,6 +459,56 @@ int wtamd_runs_region_host(int op, int64_t n, const int32_t *start, const int32_
                            int64_t m, const int32_t *m_start, const int32_t *m_finish,
                            int64_t capacity, int32_t *o_start, int32_t *o_finish, double *o_value, int64_t *n_out);
 
+/* Per-region statistics on device (csrc/wt_apply.hip): what the reference's ApplyMultiplexer (src/apply.c; the parser's
+ * `apply` / `apply_paste`, commandParser.c:266-320, 917-936) computes -- AUC meanI varI stddevI CVI maxI minI of a dataset
+ * inside every region -- as six moments per region.  Dataset and regions come in the layout of wtamd_runs_map with the SAME
+ * n_seg, segment g of one pairing with segment g of the other: start / finish (and the dataset's value, f32 or f64) are DEVICE
+ * arrays, the seg_off arrays HOST arrays of n_seg + 1 offsets.  The dataset is sorted, start < finish and DISJOINT
+ * (start[i] >= finish[i-1]: the Multiplexer's own precondition); the regions are sorted by start with start < finish and may
+ * overlap, nest or repeat -- each is evaluated on its own, as the reference does.  Anything else: WTAMD_ERR_ARG, nothing
+ * written.  Fewer than 2^31 dataset runs per call.
+ * For region [rs, rf): lo = the first run of its segment with finish > rs, hi = the first with start >= rf; the pieces are
+ * [max(s, rs), min(f, rf)) of the runs in [lo, hi).  With L the piece lengths and v the values widened to f64,
+ *     moments6 = { sum of L v, span = sum of L, T = sum of L (v - sum / span)^2, min, max, covered },
+ * the first five over the pieces whose value is not NaN, exactly as wtamd_runs_moments defines them (min / max NaN when there
+ * is none), covered = sum of L over ALL pieces, NaN-valued ones included.
+ *   WTAMD_APPLY_STRICT (`apply` without `fillIn`, the parser's default): exactly the above.
+ *   without it (`fillIn`): the (rf - rs) - covered uncovered base pairs also enter with value default_value, unless that is
+ *   NaN, as one partial {sum U d, span U, T 0, min d, max d} merged after the data; covered stays the data's.
+ * span, covered, min and max are exact; sum and T agree with exact arithmetic to rounding (pivoted sums merged pairwise in a
+ * fixed order: the same input always gives the same bits), and a region's six doubles depend on that region, its dataset
+ * segment, default_value and flags alone -- not on the other regions of the call.  moments6 is DEVICE memory, 6 doubles per
+ * region in region order.  Synchronous on `stream`; temporary memory comes from the device pool.
+ * Scratch: 16 bytes per region + 64 bytes per chunk + 8 bytes per 1024 regions + device copies of the two seg_off arrays; a
+ * region with more than 32 runs under it is cut into chunks of 2048 runs.  No start may be negative (WTAMD_ERR_ARG).
+ * Departures from the reference:
+ *   - NaN runs are skipped for varI / stddevI / CVI as for the others (the reference's VarianceCorePop never terminates on
+ *     one): the library's existing departure.
+ *   - The reference truncates the dataset's default to `float` on its buffered path (apply.c:42) but not on its long-region
+ *     path; here the double given is used.
+ *   - For regions of 10^6 bp and more (apply.c:197) the reference feeds the statistics whatever the dataset's own seek
+ *     delivers; here the runs are always clipped to the region.
+ *   - The reference buffers regions in groups and seeks the dataset to the finish of the LAST region of a group (apply.c:311):
+ *     with a reader that clips at the seek's finish, a region that reaches past it (one nested inside it follows) loses the
+ *     data beyond.  Here every region sees its dataset whole.
+ *   - A min / max tie between the default and a data value that compare equal (+-0) goes to the data. */
+#define WTAMD_APPLY_STRICT 1u
+int wtamd_runs_apply(int64_t n_seg,
+                     const int64_t *seg_off, const int32_t *start, const int32_t *finish, const void *value, int value_is_f64,
+                     const int64_t *r_seg_off, const int32_t *r_start, const int32_t *r_finish,
+                     double default_value, uint32_t flags, double *moments6, void *stream);
+/* wtamd_runs_apply of ONE segment pair held in HOST arrays, 6 doubles per region into a HOST array: device memory, copies
+ * and the call on the null stream. */
+int wtamd_runs_apply_host(int64_t n, const int32_t *start, const int32_t *finish, const double *value,
+                          int64_t n_regions, const int32_t *r_start, const int32_t *r_finish,
+                          double default_value, uint32_t flags, double *moments6);
+/* The reference's closing arithmetic over one region's six moments; HOST.  AUC is m6[0]; meanI is m6[0] / m6[1], NaN when the
+ * span is 0 (statistics.c:66-67); the rest go through wtamd_moments_finish (statistics.c:259,288-289,312-314: whatever that
+ * order gives for an empty or one-base-pair region).  NaN for an unknown statistic. */
+enum wtamd_apply_stat { WTAMD_APPLY_AUC = 0, WTAMD_APPLY_MEAN = 1, WTAMD_APPLY_VAR = 2, WTAMD_APPLY_STDDEV = 3, WTAMD_APPLY_CV = 4,
+                        WTAMD_APPLY_MAX = 5, WTAMD_APPLY_MIN = 6 };
+double wtamd_apply_finish(const double *m6, int stat);
+
 /* Run compression on device (reference CompressionWiggleIterator, unaryOps.c:235-253, which the
  * default writer applies, wigWriter.c:263-267): adjacent runs of one chromosome merge while
  * start == previous finish and (both NaN or |value - value of the group's first run| < 1e-6).
@@ -689,6 +739,19 @@ WiggleIterator *wtamd_CoverageIterator(WiggleIterator *child);
  * per-interval protocol on the host.  WTAMD_NO_DEVICE_REGION=1 (or a build of the drop-in layer without the HIP units)
  * computes the same lists with a host sweep.  A child that is not sorted by start: message and exit(1). */
 WiggleIterator *wtamd_RegionIterator(int op, WiggleIterator *source, WiggleIterator *mask);
+
+/* The reference's ApplyMultiplexer (apply.c:293-353; `apply` / `apply_paste`, commandParser.c readApply / readApplyPaste) on
+ * wtamd_runs_apply: `count` values per region, values[i] = wtamd_apply_finish(moments, stats[i]) with stats[i] a
+ * WTAMD_APPLY_* code; default_values NaN; chrom / start / finish the current region; primed with the first region, done after
+ * the last; strict as the reference's flag (0: fill-in with the dataset's default_value).  It drains regions and dataset a
+ * chromosome at a time -- in blocks from a bulk source or a reducer of this library, by pop() from anything else --, pairs
+ * chromosomes by name in strcmp order and computes the chromosome's regions in one call.  seekMultiplexer seeks both
+ * children and recomputes.  It works under SelectReduction and the reference's PasteMultiplexer.  WTAMD_NO_DEVICE_APPLY=1
+ * (or a build of the drop-in layer without the HIP units) computes the same values with a host sweep by the same rules.
+ * Refused with a message and exit(1): a dataset with `overlaps` set or one that is not disjoint, regions that are not sorted,
+ * an unknown statistic -- keep the reference's ApplyMultiplexer for those, and for ProfileMultiplexer.  The departures
+ * listed at wtamd_runs_apply hold. */
+Multiplexer *wtamd_ApplyMultiplexer(WiggleIterator *regions, const int *stats, int count, WiggleIterator *dataset, wt_bool strict);
 /* BigWig reader: the role of the reference's BigWiggleReader (src/bigWiggleReader.c:147-151) on this
  * library's own section decoder -- chromosomes in strcmp order, 1-based starts, box != 0: intervals
  * cut at the reference reader's 10 000-bp stretch edges (what `write_bg` parity needs); one producer

@@ -1,0 +1,123 @@
+// wt_abi_apply.h -- part of the DROP-IN LAYER (csrc/wt_iter_abi.cpp includes it): the reference's ApplyMultiplexer
+// (src/apply.c:293-353; the parser's `apply` / `apply_paste`) as wtamd_ApplyMultiplexer(regions, stats, count, dataset,
+// strict).  It drains regions and dataset one chromosome at a time -- in blocks where the child is a bulk source of this
+// library or one of its reducers (wtamd_iterator_next_block), by pop() otherwise --, pairs chromosomes by name in strcmp
+// order, computes six moments per region of the chromosome through the device door (wtamd_runs_apply_host,
+// csrc/wt_apply.hip) and serves one region per popMultiplexer: values[i] = wtamd_apply_finish(m6, stats[i]).
+//
+// The door is reached through a WEAK reference: a build of this layer without the HIP units (the emulated drop-in library of
+// the CPU tests) has no door and sweeps on the host by the same rules -- wap_apply_host of csrc/wt_apply.h, compiled here as
+// plain C++ --, as does WTAMD_NO_DEVICE_APPLY=1.
+//
+// Refused with a message and exit(1): a dataset with `overlaps` set or one that turns out not to be disjoint, regions that are
+// not sorted, an unknown statistic.  Such callers keep the reference's ApplyMultiplexer.
+#ifndef WT_ABI_APPLY_H_
+#define WT_ABI_APPLY_H_
+
+// the arithmetic of csrc/wt_apply.h as plain C++ (its passes and its door are not needed here)
+#ifndef WT_EMU
+#define WT_EMU 1
+#endif
+#ifndef WCV_NO_HOST
+#define WCV_NO_HOST 1
+#endif
+#include "wt_apply.h"
+
+extern "C" int wtamd_runs_apply_host(int64_t n, const int32_t *start, const int32_t *finish, const double *value, int64_t n_regions,
+                                     const int32_t *r_start, const int32_t *r_finish, double default_value, uint32_t flags,
+                                     double *moments6) __attribute__((weak));
+
+namespace {
+
+struct ApplyMux {
+    WiggleIterator *regions = nullptr, *dataset = nullptr;
+    std::vector<int> stats;
+    bool strict = true;
+    Interner names;
+    const char *chrom = nullptr;    // interned name of the chromosome being served
+    RegRuns reg, dat;
+    std::vector<double> m6;         // 6 per region of the chromosome
+    size_t j = 0;                   // the next region to serve
+};
+
+bool apm_use_device() {
+    const char *e = getenv("WTAMD_NO_DEVICE_APPLY");
+    return wtamd_runs_apply_host != nullptr && !(e && atoi(e) != 0);
+}
+
+// Every interval of the chromosome `it` stands on: whole batches of a reducer of this library, blocks of a bulk source,
+// pop() for anything else; keep == NULL: skipped.
+void apm_drain_chrom(WiggleIterator *it, const char *chrom, RegRuns *keep) {
+    if (it->pop == &red_pop) {
+        while (!it->done && strcmp(it->chrom, chrom) == 0) {
+            const int32_t *bs, *bf;
+            const double *bv;
+            const int64_t cnt = wtamd_iterator_next_block(it, nullptr, &bs, &bf, &bv);
+            if (cnt <= 0) break;
+            if (keep) {
+                keep->s.insert(keep->s.end(), bs, bs + cnt);
+                keep->f.insert(keep->f.end(), bf, bf + cnt);
+                keep->v.insert(keep->v.end(), bv, bv + cnt);
+            }
+            it->pop(it);                    // the first element of the next batch
+        }
+        return;
+    }
+    reg_drain_chrom(it, chrom, keep);
+}
+
+// Drains the next chromosome of the regions and the dataset's chromosome of the same name; false when there is none.
+bool apm_load(ApplyMux *a) {
+    WiggleIterator *reg = a->regions, *dat = a->dataset;
+    a->reg.clear(); a->dat.clear(); a->m6.clear();
+    a->j = 0;
+    if (reg->done) return false;
+    a->chrom = a->names.get(reg->chrom);
+    apm_drain_chrom(reg, a->chrom, &a->reg);
+    while (!dat->done && strcmp(dat->chrom, a->chrom) < 0) {                // chromosomes only the dataset has
+        const char *skip = a->names.get(dat->chrom);
+        apm_drain_chrom(dat, skip, nullptr);
+    }
+    if (!dat->done && strcmp(dat->chrom, a->chrom) == 0) apm_drain_chrom(dat, a->chrom, &a->dat);
+    const size_t n = a->dat.s.size(), m = a->reg.s.size();
+    a->m6.resize(6 * m);
+    const uint32_t flags = a->strict ? WTAMD_APPLY_STRICT : 0u;
+    int rc;
+    if (apm_use_device()) {
+        rc = wtamd_runs_apply_host((int64_t) n, a->dat.s.data(), a->dat.f.data(), a->dat.v.data(), (int64_t) m, a->reg.s.data(), a->reg.f.data(),
+                                   dat->default_value, flags, a->m6.data());
+        if (rc != WTAMD_OK && rc != WTAMD_ERR_ARG) die("wtamd_runs_apply");
+    } else {
+        rc = wap_apply_host((long long) n, a->dat.s.data(), a->dat.f.data(), a->dat.v.data(), (long long) m, a->reg.s.data(), a->reg.f.data(),
+                            dat->default_value, flags, a->m6.data());
+    }
+    if (rc != 0) {
+        fprintf(stderr, "wiggletools_amd: wtamd_ApplyMultiplexer: on %s the dataset overlaps itself, or a side is not sorted by start or holds an "
+                        "interval with start >= finish; keep the reference's ApplyMultiplexer for such input\n", a->chrom);
+        exit(1);
+    }
+    return true;
+}
+
+void apm_pop(Multiplexer *m) {
+    ApplyMux *a = (ApplyMux *) m->data;
+    if (a->j >= a->reg.s.size() && !apm_load(a)) { m->done = 1; return; }
+    m->chrom = (char *) a->chrom;
+    m->start = a->reg.s[a->j]; m->finish = a->reg.f[a->j];
+    for (int i = 0; i < m->count; i++) m->values[i] = wtamd_apply_finish(a->m6.data() + 6 * a->j, a->stats[(size_t) i]);
+    a->j++;
+}
+
+void apm_seek(Multiplexer *m, const char *chrom, int start, int finish) {
+    ApplyMux *a = (ApplyMux *) m->data;
+    seek(a->regions, chrom, start, finish);
+    seek(a->dataset, chrom, start, finish);
+    a->reg.clear(); a->dat.clear(); a->m6.clear();
+    a->j = 0;
+    m->done = 0;
+    apm_pop(m);
+}
+
+}  // namespace
+
+#endif  // WT_ABI_APPLY_H_

@@ -163,4 +163,19 @@ double wtamd_moments_finish(const double *m, int kind) {
     return __builtin_nan("");
 }
 
+// One region's statistic from the six moments of wtamd_runs_apply: AUC (statistics.c:103-120), meanI (:66-67: NaN on an empty
+// span), the others as wtamd_moments_finish closes them.
+double wtamd_apply_finish(const double *m, int stat) {
+    switch (stat) {
+    case WTAMD_APPLY_AUC: return m[0];
+    case WTAMD_APPLY_MEAN: return m[1] > 0 ? m[0] / m[1] : __builtin_nan("");
+    case WTAMD_APPLY_VAR: return wtamd_moments_finish(m, WTAMD_STAT_VAR);
+    case WTAMD_APPLY_STDDEV: return wtamd_moments_finish(m, WTAMD_STAT_STDDEV);
+    case WTAMD_APPLY_CV: return wtamd_moments_finish(m, WTAMD_STAT_CV);
+    case WTAMD_APPLY_MAX: return m[4];
+    case WTAMD_APPLY_MIN: return m[3];
+    default: return __builtin_nan("");
+    }
+}
+
 }  // extern "C"

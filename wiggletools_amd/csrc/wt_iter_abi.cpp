@@ -130,6 +130,7 @@ void wt_bulk_pop(WiggleIterator *wi) {
 #include "wt_abi_readers.h"
 #include "wt_abi_cover.h"
 #include "wt_abi_region.h"
+#include "wt_abi_apply.h"
 #include "wt_abi_bwdev.h"
 #include "wt_abi_ops.h"
 #include "wt_abi_integrators.h"
@@ -523,6 +524,27 @@ WiggleIterator *wtamd_RegionIterator(int op, WiggleIterator *source, WiggleItera
     wi->default_value = source->default_value;
     reg_settle(c, wi);                         // a fresh iterator already holds its first element (wiggleIterator.c:32)
     return wi;
+}
+
+// ApplyMultiplexer (apply.c:341-353) on the device door: primed with the first region, done after the last
+Multiplexer *wtamd_ApplyMultiplexer(WiggleIterator *regions, const int *stats, int count, WiggleIterator *dataset, wt_bool strict) {
+    for (int i = 0; i < count; i++)
+        if (stats[i] < WTAMD_APPLY_AUC || stats[i] > WTAMD_APPLY_MIN) {
+            fprintf(stderr, "wiggletools_amd: wtamd_ApplyMultiplexer: unknown statistic %d\n", stats[i]);
+            exit(1);
+        }
+    if (dataset->overlaps) {
+        fprintf(stderr, "wiggletools_amd: wtamd_ApplyMultiplexer: the dataset overlaps itself; keep the reference's ApplyMultiplexer for it\n");
+        exit(1);
+    }
+    ApplyMux *a = new ApplyMux();
+    a->regions = regions; a->dataset = dataset; a->strict = strict != 0;
+    a->stats.assign(stats, stats + count);
+    Multiplexer *m = newCoreMultiplexer(a, count, &apm_pop, &apm_seek);
+    m->strict = strict;
+    for (int i = 0; i < count; i++) m->default_values[i] = NAN;     // apply.c:349-350
+    popMultiplexer(m);
+    return m;
 }
 
 int64_t wtamd_iterator_next_block(WiggleIterator *wi, const char **chrom, const int32_t **start,

@@ -28,6 +28,7 @@
 
 #include "wt_host.h"
 #include "wt_devscope.h"
+#include "wt_moments_merge.h"      // WmAcc, wm_merge, WmLane, wm_add, wm_lane_acc: shared with csrc/wt_apply.h
 
 namespace {
 
@@ -35,35 +36,12 @@ namespace {
 #ifndef WM_MAX_BLOCKS
 #define WM_MAX_BLOCKS 2048          // of the bulk door: 8 blocks per CU (the pipeline launches WT_INTEG_BLOCKS per batch)
 #endif
-#define WM_NONE 0x7fffffffffffffffll
 
 struct WmPartial {          // 64 bytes
     double n, d, T, mn, mx;
     long long imn, imx;     // index of the run that set mn / mx, WM_NONE: unset
     double K;               // the launch's pivot (written by block 0)
 };
-
-struct WmAcc {
-    double n, d, T, mn, mx;
-    long long imn, imx;
-};
-
-// a := a (+) b, both about the same pivot
-__device__ __forceinline__ void wm_merge(WmAcc &a, const WmAcc &b) {
-    if (b.n > 0) {
-        if (a.n > 0) {
-            const double n = a.n + b.n;
-            const double dm = b.d / b.n - a.d / a.n;
-            a.T += b.T + dm * dm * (a.n * b.n / n);
-            a.d += b.d;
-            a.n = n;
-        } else {
-            a.n = b.n; a.d = b.d; a.T = b.T;
-        }
-    }
-    if (b.imn != WM_NONE && (a.imn == WM_NONE || b.mn < a.mn || (b.mn == a.mn && b.imn < a.imn))) { a.mn = b.mn; a.imn = b.imn; }
-    if (b.imx != WM_NONE && (a.imx == WM_NONE || b.mx > a.mx || (b.mx == a.mx && b.imx < a.imx))) { a.mx = b.mx; a.imx = b.imx; }
-}
 
 __device__ __forceinline__ long long wm_shfl_down(long long x, int s) {
     const int lo = __shfl_down((int) (x & 0xffffffffll), s), hi = __shfl_down((int) (x >> 32), s);
@@ -79,24 +57,6 @@ __device__ __forceinline__ void wm_wave_reduce(WmAcc &a) {
         b.imn = wm_shfl_down(a.imn, s); b.imx = wm_shfl_down(a.imx, s);
         wm_merge(a, b);                     // (lanes whose partner lies past the wavefront read their own value back and are
     }                                       //  never read again: lane 0's tree only has partners inside the wavefront)
-}
-
-struct WmLane {
-    double s0, s1, s2, k, mn, mx;
-    long long imn, imx;
-    bool have;
-};
-
-__device__ __forceinline__ void wm_add(WmLane &a, long long r, int st, int fi, double v) {
-    if (v == v) {                           // NaN runs are skipped
-        if (!a.have) { a.k = v; a.have = true; }
-        const double L = (double) (fi - st), e = v - a.k, Le = L * e;
-        a.s0 += L;
-        a.s1 += Le;
-        a.s2 += Le * e;
-        if (a.imn == WM_NONE || v < a.mn) { a.mn = v; a.imn = r; }
-        if (a.imx == WM_NONE || v > a.mx) { a.mx = v; a.imx = r; }
-    }
 }
 
 __global__ void __launch_bounds__(WM_BLOCK) wt_moments_kernel(const int32_t *__restrict__ start, const int32_t *__restrict__ finish,
@@ -135,11 +95,7 @@ __global__ void __launch_bounds__(WM_BLOCK) wt_moments_kernel(const int32_t *__r
     }
     for (long long r = done + me; r < n; r += lanes) wm_add(a, r, start[r], finish[r], value[r]);
 
-    WmAcc c;
-    c.n = a.s0;
-    c.T = a.s0 > 0 ? a.s2 - a.s1 * a.s1 / a.s0 : 0.0;
-    c.d = a.s1 + (a.k - K) * a.s0;
-    c.mn = a.mn; c.mx = a.mx; c.imn = a.imn; c.imx = a.imx;
+    WmAcc c = wm_lane_acc(a, K);
     wm_wave_reduce(c);
     if ((t & 63) == 0) red[w] = c;
     __syncthreads();

@@ -113,6 +113,17 @@ def region_iterator(op, source, mask):
     return L.wtamd_RegionIterator(REGION_OPS[op] if isinstance(op, str) else int(op), source, mask)
 
 
+def apply_multiplexer(regions, stats, dataset, strict=True):
+    """wtamd_ApplyMultiplexer: the reference's `apply` of `dataset` inside every region of `regions`; stats: names of
+    engine.APPLY_STATS or raw codes.  A Multiplexer: read it with popMultiplexer or under SelectReduction."""
+    from .engine import APPLY_STATS
+    L = _bind()
+    L.wtamd_ApplyMultiplexer.restype = C.c_void_p
+    L.wtamd_ApplyMultiplexer.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_char]
+    codes = (C.c_int * len(stats))(*[APPLY_STATS[s] if isinstance(s, str) else int(s) for s in stats])
+    return L.wtamd_ApplyMultiplexer(regions, codes, len(stats), dataset, b"\x01" if strict else b"\x00")
+
+
 def bigwig_reader(path, box=True):
     """wtamd_BigWiggleReader: the reference's BigWiggleReader role (bigWiggleReader.c:147-151), bulk-capable."""
     return _bind().wtamd_BigWiggleReader(path.encode(), int(box))

@@ -152,6 +152,50 @@ def region_runlists(op, source: RunLists, mask: RunLists):
     return out
 
 
+APPLY_STATS = {"AUC": 0, "meanI": 1, "varI": 2, "stddevI": 3, "CVI": 4, "maxI": 5, "minI": 6}      # WTAMD_APPLY_*
+APPLY_STRICT = 1
+
+
+def _apply_door(data, regions, default=0.0, strict=True, flags=None):
+    """wtamd_runs_apply over every segment pair of `data` and `regions`.  Returns (rc, (n, 6) array); the array starts out
+    filled with -1 and a refused call leaves it so."""
+    import torch
+    dev = torch.device("cuda", torch.cuda.current_device())
+    n_seg = data.n_chrom * data.n_tracks
+    if regions.n_chrom * regions.n_tracks != n_seg:
+        raise ValueError("apply: data and regions must have the same number of segments")
+    n_r = int(regions.seg_off[-1])
+    seg, rseg = np.ascontiguousarray(data.seg_off, np.int64), np.ascontiguousarray(regions.seg_off, np.int64)
+    s = torch.from_numpy(np.ascontiguousarray(data.start, np.int32)).to(dev)
+    f = torch.from_numpy(np.ascontiguousarray(data.finish, np.int32)).to(dev)
+    v = torch.from_numpy(np.ascontiguousarray(data.value)).to(dev)
+    rs = torch.from_numpy(np.ascontiguousarray(regions.start, np.int32)).to(dev)
+    rf = torch.from_numpy(np.ascontiguousarray(regions.finish, np.int32)).to(dev)
+    out = torch.full((max(n_r, 1), 6), -1.0, dtype=torch.float64, device=dev)
+    fl = (APPLY_STRICT if strict else 0) if flags is None else int(flags)
+    rc = _lib.lib().wtamd_runs_apply(n_seg, seg.ctypes.data, s.data_ptr(), f.data_ptr(), v.data_ptr(),
+                                     1 if data.value.dtype == np.float64 else 0, rseg.ctypes.data, rs.data_ptr(), rf.data_ptr(),
+                                     float(default), fl, out.data_ptr(), None)
+    return rc, out[:n_r].cpu().numpy()
+
+
+def apply_runlists(data: RunLists, regions: RunLists, default=0.0, strict=True):
+    """The reference's `apply` (ApplyMultiplexer, src/apply.c) as six moments per region, on device (wtamd_runs_apply):
+    {sum of L v, span, T, min, max, covered} of every segment of `data` inside every region of the segment of `regions` at the
+    same place, an (n, 6) array in region order.  strict=False is `fillIn`: uncovered base pairs enter with `default`.  The
+    data must not overlap itself (include/wiggletools_amd.h); apply_finish turns a row into a statistic."""
+    rc, out = _apply_door(data, regions, default, strict)
+    _lib.check(rc)
+    return out
+
+
+def apply_finish(m6, stat):
+    """AUC, meanI, varI, stddevI, CVI, maxI or minI (a name of APPLY_STATS or a raw code) from one row of apply_runlists."""
+    m = np.ascontiguousarray(m6, np.float64)
+    assert m.shape == (6,)
+    return _lib.lib().wtamd_apply_finish(m.ctypes.data, APPLY_STATS[stat] if isinstance(stat, str) else int(stat))
+
+
 class TrackSet:
     """N tracks resident in HBM (wtamd_trackset)."""
 
