@@ -509,6 +509,48 @@ enum wtamd_apply_stat { WTAMD_APPLY_AUC = 0, WTAMD_APPLY_MEAN = 1, WTAMD_APPLY_V
                         WTAMD_APPLY_MAX = 5, WTAMD_APPLY_MIN = 6 };
 double wtamd_apply_finish(const double *m6, int stat);
 
+/* Region profiles on device (csrc/wt_profile.hip): what the reference's ProfileMultiplexer (src/apply.c:355-366; the parser's
+ * `profile` / `profiles`, commandParser.c:862-905) computes through regionProfile (src/plots.c:27-64) -- the dataset under
+ * every region squeezed or stretched onto `width` bins.  Dataset and regions exactly as for wtamd_runs_apply (same layout, the
+ * SAME n_seg, dataset sorted, start < finish and DISJOINT, regions sorted by start and free to overlap, nest or repeat, no
+ * negative start, fewer than 2^31 runs) and width >= 1; anything else, or an unknown flag bit: WTAMD_ERR_ARG, nothing written.
+ * The rule, never strict.  Region [rs, rf), L = rf - rs, W = width, c = W / (double) L, positions relative to rs.  The
+ * reference serves one run [i, i + 1) with the dataset's value for every covered position i, and ONE run [a, b) with
+ * default_value for every maximal uncovered stretch (before the first run and after the last included).  A run [a, b) with
+ * value v: a NaN v is skipped; start = round(a c), finish = round(b c) (C's round on the double product); finish <= start
+ * becomes start + 1, finish > W becomes W; every bin of [start, finish) gets v / (finish - start).
+ * Consequences (the reference's, reproduced):
+ *   - c <= 1: every covered position lands in the one bin round(i c) with its full value; bins are centred, so bin 0 collects
+ *     about half as many positions as the others, and with L >= 2 W the last positions have round(i c) == W and are dropped
+ *     (L = 20, W = 4, value 1 everywhere: 3 5 5 5).
+ *   - c > 1: every bin has exactly one contributor and holds v / n, bit for bit.
+ *   - An uncovered stretch counts as ONE sample of the default, spread over its bins, however long it is (L = 20, W = 4, runs
+ *     [2,5) = 2 and [10,18) = 1, default 0.5: 2.5 4.5 3 5 -- the trailing stretch [18,20) starts at bin 4 and vanishes).
+ * profile is DEVICE memory: width doubles per region, row-major in region order -- or, with WTAMD_PROFILE_SUM (`profile`),
+ * width doubles: the column sums of all rows of all segments, merged pairwise, the lower region first, in ONE tree over the
+ * region index whatever the batch.  A bin's terms are added in position order (a bin with more than 32 runs under it: 64
+ * contiguous shares merged pairwise): the same input always gives the same bits, and a region's row depends on that region,
+ * its dataset segment, default_value and width alone.  Synchronous on `stream`; temporary memory from the device pool.
+ * Regions are processed in batches (a power of two of regions, at most 2^22 bins, at least one region; WTAMD_PROFILE_BATCH=<n>
+ * sets the regions per batch).  Scratch: 16 bytes per region + 40 bytes per 256 bins of a batch + device copies of the two
+ * seg_off arrays; with WTAMD_PROFILE_SUM also 8 bytes x (bins of a batch + width x (2 + log2 of the number of batches)).
+ * Departures from the reference, as for wtamd_runs_apply:
+ *   - The reference truncates the dataset's default to `float` (apply.c:42); here the double given is used.
+ *   - The reference seeks the dataset to the finish of the LAST region of a buffered group (apply.c:311), so a region reaching
+ *     past a nested one loses data; here every region sees its dataset whole.
+ *   - Regions of 10^6 bp and more (apply.c:197) take the reference's unbuffered path, which feeds regionProfile absolute
+ *     coordinates; here the rule above holds at every length. */
+#define WTAMD_PROFILE_SUM 1u
+int wtamd_runs_profile(int64_t n_seg,
+                       const int64_t *seg_off, const int32_t *start, const int32_t *finish, const void *value, int value_is_f64,
+                       const int64_t *r_seg_off, const int32_t *r_start, const int32_t *r_finish,
+                       int32_t width, double default_value, uint32_t flags, double *profile, void *stream);
+/* wtamd_runs_profile of ONE segment pair held in HOST arrays, the rows (or their sum) into a HOST array: device memory, copies
+ * and the call on the null stream. */
+int wtamd_runs_profile_host(int64_t n, const int32_t *start, const int32_t *finish, const double *value,
+                            int64_t n_regions, const int32_t *r_start, const int32_t *r_finish,
+                            int32_t width, double default_value, uint32_t flags, double *profile);
+
 /* Run compression on device (reference CompressionWiggleIterator, unaryOps.c:235-253, which the
  * default writer applies, wigWriter.c:263-267): adjacent runs of one chromosome merge while
  * start == previous finish and (both NaN or |value - value of the group's first run| < 1e-6).
@@ -749,9 +791,16 @@ WiggleIterator *wtamd_RegionIterator(int op, WiggleIterator *source, WiggleItera
  * children and recomputes.  It works under SelectReduction and the reference's PasteMultiplexer.  WTAMD_NO_DEVICE_APPLY=1
  * (or a build of the drop-in layer without the HIP units) computes the same values with a host sweep by the same rules.
  * Refused with a message and exit(1): a dataset with `overlaps` set or one that is not disjoint, regions that are not sorted,
- * an unknown statistic -- keep the reference's ApplyMultiplexer for those, and for ProfileMultiplexer.  The departures
+ * an unknown statistic -- keep the reference's ApplyMultiplexer for those.  The departures
  * listed at wtamd_runs_apply hold. */
 Multiplexer *wtamd_ApplyMultiplexer(WiggleIterator *regions, const int *stats, int count, WiggleIterator *dataset, wt_bool strict);
+/* The reference's ProfileMultiplexer (apply.c:355-366; `profile` / `profiles`, commandParser.c readProfile / readProfiles) on
+ * wtamd_runs_profile: count = width values per region, the region's row; default_values NaN; never strict.  It drains, pairs
+ * chromosomes, serves one region per popMultiplexer and seeks exactly as wtamd_ApplyMultiplexer does (the same code).
+ * WTAMD_NO_DEVICE_PROFILE=1 (or a build of the drop-in layer without the HIP units) computes the same bits with a host sweep.
+ * Refused with a message and exit(1): width < 1, a dataset with `overlaps` set or one that is not disjoint, regions that are not
+ * sorted.  The departures listed at wtamd_runs_profile hold. */
+Multiplexer *wtamd_ProfileMultiplexer(WiggleIterator *regions, int width, WiggleIterator *dataset);
 /* BigWig reader: the role of the reference's BigWiggleReader (src/bigWiggleReader.c:147-151) on this
  * library's own section decoder -- chromosomes in strcmp order, 1-based starts, box != 0: intervals
  * cut at the reference reader's 10 000-bp stretch edges (what `write_bg` parity needs); one producer

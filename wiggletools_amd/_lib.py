@@ -83,6 +83,10 @@ def lib():
                                    C.c_double, C.c_uint32, C.c_void_p, C.c_void_p]
     L.wtamd_runs_apply_host.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_double,
                                         C.c_uint32, C.c_void_p]
+    L.wtamd_runs_profile.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_int32, C.c_double, C.c_uint32, C.c_void_p, C.c_void_p]
+    L.wtamd_runs_profile_host.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
+                                          C.c_double, C.c_uint32, C.c_void_p]
     L.wtamd_apply_finish.argtypes = [C.c_void_p, C.c_int]
     L.wtamd_apply_finish.restype = C.c_double
     L.wtamd_map_default.argtypes = [C.c_int, C.c_double, C.c_double]

@@ -66,19 +66,26 @@ void apm_drain_chrom(WiggleIterator *it, const char *chrom, RegRuns *keep) {
     reg_drain_chrom(it, chrom, keep);
 }
 
-// Drains the next chromosome of the regions and the dataset's chromosome of the same name; false when there is none.
-bool apm_load(ApplyMux *a) {
-    WiggleIterator *reg = a->regions, *dat = a->dataset;
-    a->reg.clear(); a->dat.clear(); a->m6.clear();
-    a->j = 0;
+// Drains the next chromosome of the regions and the dataset's chromosome of the same name (wt_abi_profile.h shares it); false
+// when there is none.
+bool apm_drain_pair(WiggleIterator *reg, WiggleIterator *dat, Interner &names, const char **chrom, RegRuns *reg_runs, RegRuns *dat_runs) {
+    reg_runs->clear(); dat_runs->clear();
     if (reg->done) return false;
-    a->chrom = a->names.get(reg->chrom);
-    apm_drain_chrom(reg, a->chrom, &a->reg);
-    while (!dat->done && strcmp(dat->chrom, a->chrom) < 0) {                // chromosomes only the dataset has
-        const char *skip = a->names.get(dat->chrom);
+    *chrom = names.get(reg->chrom);
+    apm_drain_chrom(reg, *chrom, reg_runs);
+    while (!dat->done && strcmp(dat->chrom, *chrom) < 0) {                  // chromosomes only the dataset has
+        const char *skip = names.get(dat->chrom);
         apm_drain_chrom(dat, skip, nullptr);
     }
-    if (!dat->done && strcmp(dat->chrom, a->chrom) == 0) apm_drain_chrom(dat, a->chrom, &a->dat);
+    if (!dat->done && strcmp(dat->chrom, *chrom) == 0) apm_drain_chrom(dat, *chrom, dat_runs);
+    return true;
+}
+
+bool apm_load(ApplyMux *a) {
+    WiggleIterator *dat = a->dataset;
+    a->m6.clear();
+    a->j = 0;
+    if (!apm_drain_pair(a->regions, dat, a->names, &a->chrom, &a->reg, &a->dat)) return false;
     const size_t n = a->dat.s.size(), m = a->reg.s.size();
     a->m6.resize(6 * m);
     const uint32_t flags = a->strict ? WTAMD_APPLY_STRICT : 0u;

@@ -131,6 +131,7 @@ void wt_bulk_pop(WiggleIterator *wi) {
 #include "wt_abi_cover.h"
 #include "wt_abi_region.h"
 #include "wt_abi_apply.h"
+#include "wt_abi_profile.h"
 #include "wt_abi_bwdev.h"
 #include "wt_abi_ops.h"
 #include "wt_abi_integrators.h"
@@ -543,6 +544,25 @@ Multiplexer *wtamd_ApplyMultiplexer(WiggleIterator *regions, const int *stats, i
     Multiplexer *m = newCoreMultiplexer(a, count, &apm_pop, &apm_seek);
     m->strict = strict;
     for (int i = 0; i < count; i++) m->default_values[i] = NAN;     // apply.c:349-350
+    popMultiplexer(m);
+    return m;
+}
+
+// ProfileMultiplexer (apply.c:355-366) on the device door: primed with the first region, done after the last
+Multiplexer *wtamd_ProfileMultiplexer(WiggleIterator *regions, int width, WiggleIterator *dataset) {
+    if (width < 1) {
+        fprintf(stderr, "wiggletools_amd: wtamd_ProfileMultiplexer: width %d\n", width);
+        exit(1);
+    }
+    if (dataset->overlaps) {
+        fprintf(stderr, "wiggletools_amd: wtamd_ProfileMultiplexer: the dataset overlaps itself; keep the reference's ProfileMultiplexer for it\n");
+        exit(1);
+    }
+    ProfileMux *a = new ProfileMux();
+    a->regions = regions; a->dataset = dataset; a->width = width;
+    Multiplexer *m = newCoreMultiplexer(a, width, &prm_pop, &prm_seek);
+    m->strict = 0;                                                  // apply.c:359
+    for (int i = 0; i < width; i++) m->default_values[i] = NAN;     // apply.c:362-363
     popMultiplexer(m);
     return m;
 }

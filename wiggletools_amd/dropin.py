@@ -124,6 +124,15 @@ def apply_multiplexer(regions, stats, dataset, strict=True):
     return L.wtamd_ApplyMultiplexer(regions, codes, len(stats), dataset, b"\x01" if strict else b"\x00")
 
 
+def profile_multiplexer(regions, width, dataset):
+    """wtamd_ProfileMultiplexer: the reference's `profiles` of `dataset` under every region of `regions` on `width` bins.  A
+    Multiplexer: read it with popMultiplexer or under SelectReduction."""
+    L = _bind()
+    L.wtamd_ProfileMultiplexer.restype = C.c_void_p
+    L.wtamd_ProfileMultiplexer.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    return L.wtamd_ProfileMultiplexer(regions, int(width), dataset)
+
+
 def bigwig_reader(path, box=True):
     """wtamd_BigWiggleReader: the reference's BigWiggleReader role (bigWiggleReader.c:147-151), bulk-capable."""
     return _bind().wtamd_BigWiggleReader(path.encode(), int(box))

@@ -196,6 +196,44 @@ def apply_finish(m6, stat):
     return _lib.lib().wtamd_apply_finish(m.ctypes.data, APPLY_STATS[stat] if isinstance(stat, str) else int(stat))
 
 
+PROFILE_SUM = 1
+
+
+def _profile_door(data, regions, width, default=0.0, sum=False, flags=None):
+    """wtamd_runs_profile over every segment pair of `data` and `regions`.  Returns (rc, (n, width) array, or (width,) in sum
+    mode); the array starts out filled with -1 and a refused call leaves it so."""
+    import torch
+    dev = torch.device("cuda", torch.cuda.current_device())
+    n_seg = data.n_chrom * data.n_tracks
+    if regions.n_chrom * regions.n_tracks != n_seg:
+        raise ValueError("profile: data and regions must have the same number of segments")
+    n_r = int(regions.seg_off[-1])
+    seg, rseg = np.ascontiguousarray(data.seg_off, np.int64), np.ascontiguousarray(regions.seg_off, np.int64)
+    s = torch.from_numpy(np.ascontiguousarray(data.start, np.int32)).to(dev)
+    f = torch.from_numpy(np.ascontiguousarray(data.finish, np.int32)).to(dev)
+    v = torch.from_numpy(np.ascontiguousarray(data.value)).to(dev)
+    rs = torch.from_numpy(np.ascontiguousarray(regions.start, np.int32)).to(dev)
+    rf = torch.from_numpy(np.ascontiguousarray(regions.finish, np.int32)).to(dev)
+    fl = (PROFILE_SUM if sum else 0) if flags is None else int(flags)
+    rows = 1 if fl & PROFILE_SUM else n_r
+    out = torch.full((max(rows, 1), max(int(width), 1)), -1.0, dtype=torch.float64, device=dev)
+    rc = _lib.lib().wtamd_runs_profile(n_seg, seg.ctypes.data, s.data_ptr(), f.data_ptr(), v.data_ptr(),
+                                       1 if data.value.dtype == np.float64 else 0, rseg.ctypes.data, rs.data_ptr(), rf.data_ptr(),
+                                       int(width), float(default), fl, out.data_ptr(), None)
+    out = out.cpu().numpy()
+    return rc, (out[0] if fl & PROFILE_SUM else out[:n_r])
+
+
+def profile_runlists(data: RunLists, regions: RunLists, width, default=0.0, sum=False):
+    """The reference's `profiles` (ProfileMultiplexer, src/apply.c, over regionProfile, src/plots.c) on device
+    (wtamd_runs_profile): every segment of `data` under every region of the segment of `regions` at the same place, squeezed or
+    stretched onto `width` bins -- an (n, width) array in region order; sum=True is `profile`: the (width,) column sums.
+    Uncovered stretches enter as one sample of `default` each.  The data must not overlap itself (include/wiggletools_amd.h)."""
+    rc, out = _profile_door(data, regions, width, default, sum)
+    _lib.check(rc)
+    return out
+
+
 class TrackSet:
     """N tracks resident in HBM (wtamd_trackset)."""
 
