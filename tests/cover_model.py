@@ -131,7 +131,7 @@ def emu_lib():
     global _emu
     if _emu is None:
         so = os.path.join(HERE, "libcover_emu.so")
-        deps = [os.path.join(HERE, "cover_emu.cpp"), os.path.join(ROOT, "wiggletools_amd", "csrc", "wt_cover.h")]
+        deps = [os.path.join(HERE, "cover_emu.cpp"), os.path.join(HERE, "emu", "runs_launcher.h"), os.path.join(ROOT, "wiggletools_amd", "csrc", "wt_cover.h")]
         if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
             tmp = "%s.tmp.%d" % (so, os.getpid())
             subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-function", "-o", tmp, deps[0]])

@@ -346,7 +346,7 @@ def emu_lib():
     global _emu
     if _emu is None:
         so = os.path.join(HERE, "libprofile_emu.so")
-        deps = [os.path.join(HERE, "profile_emu.cpp"), HEADER] + [os.path.join(CSRC, h) for h in ("wt_apply.h", "wt_region.h", "wt_cover.h", "wt_moments_merge.h")]
+        deps = [os.path.join(HERE, "profile_emu.cpp"), os.path.join(HERE, "emu", "runs_launcher.h"), HEADER] + [os.path.join(CSRC, h) for h in ("wt_apply.h", "wt_region.h", "wt_cover.h", "wt_moments_merge.h")]
         if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
             tmp = "%s.tmp.%d" % (so, os.getpid())
             subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas",

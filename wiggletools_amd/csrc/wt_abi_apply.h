@@ -29,21 +29,11 @@ extern "C" int wtamd_runs_apply_host(int64_t n, const int32_t *start, const int3
 
 namespace {
 
-struct ApplyMux {
-    WiggleIterator *regions = nullptr, *dataset = nullptr;
+struct ApplyMux : RegionMux {       // (csrc/wt_abi_runs.h; res: 6 moments per region of the chromosome)
     std::vector<int> stats;
     bool strict = true;
-    Interner names;
-    const char *chrom = nullptr;    // interned name of the chromosome being served
-    RegRuns reg, dat;
-    std::vector<double> m6;         // 6 per region of the chromosome
-    size_t j = 0;                   // the next region to serve
+    ApplyMux() : RegionMux("Apply") {}
 };
-
-bool apm_use_device() {
-    const char *e = getenv("WTAMD_NO_DEVICE_APPLY");
-    return wtamd_runs_apply_host != nullptr && !(e && atoi(e) != 0);
-}
 
 // Every interval of the chromosome `it` stands on: whole batches of a reducer of this library, blocks of a bulk source,
 // pop() for anything else; keep == NULL: skipped.
@@ -83,46 +73,32 @@ bool apm_drain_pair(WiggleIterator *reg, WiggleIterator *dat, Interner &names, c
 
 bool apm_load(ApplyMux *a) {
     WiggleIterator *dat = a->dataset;
-    a->m6.clear();
+    a->res.clear();
     a->j = 0;
     if (!apm_drain_pair(a->regions, dat, a->names, &a->chrom, &a->reg, &a->dat)) return false;
     const size_t n = a->dat.s.size(), m = a->reg.s.size();
-    a->m6.resize(6 * m);
+    a->res.resize(6 * m);
     const uint32_t flags = a->strict ? WTAMD_APPLY_STRICT : 0u;
     int rc;
-    if (apm_use_device()) {
+    if (wt_use_device((const void *) wtamd_runs_apply_host, "WTAMD_NO_DEVICE_APPLY")) {
         rc = wtamd_runs_apply_host((int64_t) n, a->dat.s.data(), a->dat.f.data(), a->dat.v.data(), (int64_t) m, a->reg.s.data(), a->reg.f.data(),
-                                   dat->default_value, flags, a->m6.data());
+                                   dat->default_value, flags, a->res.data());
         if (rc != WTAMD_OK && rc != WTAMD_ERR_ARG) die("wtamd_runs_apply");
     } else {
         rc = wap_apply_host((long long) n, a->dat.s.data(), a->dat.f.data(), a->dat.v.data(), (long long) m, a->reg.s.data(), a->reg.f.data(),
-                            dat->default_value, flags, a->m6.data());
+                            dat->default_value, flags, a->res.data());
     }
-    if (rc != 0) {
-        fprintf(stderr, "wiggletools_amd: wtamd_ApplyMultiplexer: on %s the dataset overlaps itself, or a side is not sorted by start or holds an "
-                        "interval with start >= finish; keep the reference's ApplyMultiplexer for such input\n", a->chrom);
-        exit(1);
-    }
+    if (rc != 0) rmx_refuse(a);
     return true;
 }
 
 void apm_pop(Multiplexer *m) {
-    ApplyMux *a = (ApplyMux *) m->data;
+    ApplyMux *a = (ApplyMux *) (RegionMux *) m->data;
     if (a->j >= a->reg.s.size() && !apm_load(a)) { m->done = 1; return; }
     m->chrom = (char *) a->chrom;
     m->start = a->reg.s[a->j]; m->finish = a->reg.f[a->j];
-    for (int i = 0; i < m->count; i++) m->values[i] = wtamd_apply_finish(a->m6.data() + 6 * a->j, a->stats[(size_t) i]);
+    for (int i = 0; i < m->count; i++) m->values[i] = wtamd_apply_finish(a->res.data() + 6 * a->j, a->stats[(size_t) i]);
     a->j++;
-}
-
-void apm_seek(Multiplexer *m, const char *chrom, int start, int finish) {
-    ApplyMux *a = (ApplyMux *) m->data;
-    seek(a->regions, chrom, start, finish);
-    seek(a->dataset, chrom, start, finish);
-    a->reg.clear(); a->dat.clear(); a->m6.clear();
-    a->j = 0;
-    m->done = 0;
-    apm_pop(m);
 }
 
 }  // namespace

@@ -3,7 +3,7 @@
 // start only, as the reference's BED / BAM / bigBed readers deliver them); wtamd_CoverageIterator is the reference's
 // CoverageWiggleIterator (src/unaryOps.c:303-375) as a bulk source: it drains its child one chromosome at a time, computes
 // the chromosome's depth track through the device door (wtamd_runs_coverage, csrc/wt_cover.hip) and serves the finished run
-// list -- to the library's Multiplexer in blocks, to wtamd_iterator_next_block, and to a foreign pop() one run at a time.
+// list as a ServedRuns (csrc/wt_abi_runs.h).
 //
 // The door is reached through a WEAK reference: a build of this layer without the HIP units (the emulated drop-in library of
 // the CPU tests) has no door and sweeps on the host instead, as does WTAMD_NO_DEVICE_COVERAGE=1.  Either way the result is
@@ -112,117 +112,47 @@ void cov_host_sweep(const std::vector<int32_t> &s, const std::vector<int32_t> &f
     }
 }
 
-struct CovIter {
-    BulkSource hdr;                 // must stay first (see wt_bulk_pop)
+struct CovIter : ServedRuns {      // (csrc/wt_abi_runs.h: BulkSource hdr stays first)
     WiggleIterator *child = nullptr;
     Interner names;
-    const char *chrom = nullptr;    // interned name of the chromosome being served
-    std::vector<int32_t> in_s, in_f;
-    std::vector<int32_t> s, f;      // the chromosome's depth track
-    std::vector<double> vd;
-    std::vector<float> vf;          // ... as float32 for the Multiplexer's blocks: exact up to a depth of 2^24
-    int64_t j = 0;
-    bool done = false;
-    bool block_out = false;         // wtamd_iterator_next_block handed out [j, end): the next call moves past it
+    RegRuns in;                     // the chromosome's intervals (no values: the depth counts them)
 };
 
-bool cov_use_device() {
-    const char *e = getenv("WTAMD_NO_DEVICE_COVERAGE");
-    return wtamd_runs_coverage_host != nullptr && !(e && atoi(e) != 0);
-}
-
-// Drains the next chromosome(s) of the child until one has a depth track; done when the child is exhausted.
-void cov_load(CovIter *c) {
+// Drains the next chromosome(s) of the child until one has a depth track (float32 holds it exactly up to a depth of 2^24);
+// done when the child is exhausted.
+void cov_load(ServedRuns *r) {
+    CovIter *c = (CovIter *) r;
     WiggleIterator *it = c->child;
-    c->s.clear(); c->f.clear(); c->vd.clear(); c->vf.clear();
-    c->j = 0;
     while (!it->done) {
         c->chrom = c->names.get(it->chrom);
-        c->in_s.clear(); c->in_f.clear();
-        BulkSource *bulk = it->pop == &wt_bulk_pop ? (BulkSource *) it->data : nullptr;
-        while (!it->done && strcmp(it->chrom, c->chrom) == 0) {
-            const int32_t *bs, *bf;
-            const float *bv;
-            const int64_t cnt = bulk ? bulk->peek(bulk, &bs, &bf, &bv) : 0;
-            if (cnt > 0) {              // a block of the current chromosome
-                c->in_s.insert(c->in_s.end(), bs, bs + cnt);
-                c->in_f.insert(c->in_f.end(), bf, bf + cnt);
-                bulk->advance(bulk, it, cnt);
-            } else {
-                c->in_s.push_back(it->start); c->in_f.push_back(it->finish);
-                it->pop(it);
-            }
-        }
-        const size_t n = c->in_s.size();
+        c->in.clear();
+        reg_drain_chrom(it, c->chrom, &c->in, false);
+        const size_t n = c->in.s.size();
         for (size_t q = 0; q < n; q++)
-            if (c->in_s[q] >= c->in_f[q] || (q > 0 && c->in_s[q] < c->in_s[q - 1])) {
+            if (c->in.s[q] >= c->in.f[q] || (q > 0 && c->in.s[q] < c->in.s[q - 1])) {
                 fprintf(stderr, "wiggletools_amd: wtamd_CoverageIterator: %s is not sorted by start, or holds an interval with start >= finish\n", c->chrom);
                 exit(1);
             }
-        if (cov_use_device()) {
+        RegRuns &o = c->out;
+        if (wt_use_device((const void *) wtamd_runs_coverage_host, "WTAMD_NO_DEVICE_COVERAGE")) {
             const int64_t cap = 2 * (int64_t) n - 1;
-            c->s.resize((size_t) cap); c->f.resize((size_t) cap); c->vd.resize((size_t) cap);
+            o.s.resize((size_t) cap); o.f.resize((size_t) cap); o.v.resize((size_t) cap);
             int64_t n_out = 0;
-            if (wtamd_runs_coverage_host((int64_t) n, c->in_s.data(), c->in_f.data(), cap, c->s.data(), c->f.data(), c->vd.data(), &n_out) != WTAMD_OK)
+            if (wtamd_runs_coverage_host((int64_t) n, c->in.s.data(), c->in.f.data(), cap, o.s.data(), o.f.data(), o.v.data(), &n_out) != WTAMD_OK)
                 die("wtamd_runs_coverage");
-            c->s.resize((size_t) n_out); c->f.resize((size_t) n_out); c->vd.resize((size_t) n_out);
+            o.s.resize((size_t) n_out); o.f.resize((size_t) n_out); o.v.resize((size_t) n_out);
         } else {
-            cov_host_sweep(c->in_s, c->in_f, c->s, c->f, c->vd);
+            cov_host_sweep(c->in.s, c->in.f, o.s, o.f, o.v);
         }
-        if (!c->s.empty()) {
-            c->vf.assign(c->vd.begin(), c->vd.end());
-            return;
-        }
+        if (!o.s.empty()) return;
     }
     c->done = true;
 }
 
-void cov_settle(CovIter *c, WiggleIterator *wi) {
-    if (!c->done && c->j >= (int64_t) c->s.size()) cov_load(c);
-    if (c->done) { wi->done = 1; return; }
-    wi->chrom = (char *) c->chrom;
-    wi->start = c->s[(size_t) c->j]; wi->finish = c->f[(size_t) c->j];
-    wi->value = c->vd[(size_t) c->j];
-}
-
-int64_t cov_peek(BulkSource *b, const int32_t **s, const int32_t **f, const float **v) {
-    CovIter *c = (CovIter *) b;
-    if (c->done || c->block_out || c->j >= (int64_t) c->s.size()) return 0;
-    *s = c->s.data() + c->j; *f = c->f.data() + c->j; *v = c->vf.data() + c->j;
-    return (int64_t) c->s.size() - c->j;
-}
-
-void cov_advance(BulkSource *b, WiggleIterator *wi, int64_t k) {
-    CovIter *c = (CovIter *) b;
-    if (c->done) { wi->done = 1; return; }
-    if (c->block_out) { c->block_out = false; c->j = (int64_t) c->s.size(); }      // the block's runs have been taken
-    else c->j += k;
-    cov_settle(c, wi);
-}
-
 void cov_seek(WiggleIterator *wi, const char *chrom, int start, int finish) {
-    CovIter *c = (CovIter *) wi->data;
+    CovIter *c = (CovIter *) (ServedRuns *) wi->data;
     seek(c->child, chrom, start, finish);
-    c->done = false;
-    c->block_out = false;
-    c->s.clear(); c->f.clear(); c->vd.clear(); c->vf.clear();
-    c->j = 0;
-    wi->done = 0;
-    cov_settle(c, wi);
-}
-
-bool cov_is(WiggleIterator *wi) { return wi && wi->pop == &wt_bulk_pop && wi->data && ((BulkSource *) wi->data)->peek == &cov_peek; }
-
-// wtamd_iterator_next_block over a coverage iterator: the runs from the current element to the end of its chromosome
-int64_t cov_next_block(WiggleIterator *wi, const char **chrom, const int32_t **start, const int32_t **finish, const double **value) {
-    CovIter *c = (CovIter *) wi->data;
-    if (c->block_out) cov_advance(&c->hdr, wi, 0);
-    if (wi->done) return 0;
-    const int64_t n = (int64_t) c->s.size() - c->j;
-    if (chrom) *chrom = c->chrom;
-    *start = c->s.data() + c->j; *finish = c->f.data() + c->j; *value = c->vd.data() + c->j;
-    c->block_out = true;
-    return n;
+    srv_restart(c, wi);
 }
 
 }  // namespace

@@ -23,62 +23,38 @@ extern "C" int wtamd_runs_profile_host(int64_t n, const int32_t *start, const in
 
 namespace {
 
-struct ProfileMux {
-    WiggleIterator *regions = nullptr, *dataset = nullptr;
+struct ProfileMux : RegionMux {     // (csrc/wt_abi_runs.h; res: width bins per region of the chromosome)
     int width = 1;
-    Interner names;
-    const char *chrom = nullptr;    // interned name of the chromosome being served
-    RegRuns reg, dat;
-    std::vector<double> rows;       // width per region of the chromosome
-    size_t j = 0;                   // the next region to serve
+    ProfileMux() : RegionMux("Profile") {}
 };
-
-bool prm_use_device() {
-    const char *e = getenv("WTAMD_NO_DEVICE_PROFILE");
-    return wtamd_runs_profile_host != nullptr && !(e && atoi(e) != 0);
-}
 
 bool prm_load(ProfileMux *a) {
     WiggleIterator *dat = a->dataset;
-    a->rows.clear();
+    a->res.clear();
     a->j = 0;
     if (!apm_drain_pair(a->regions, dat, a->names, &a->chrom, &a->reg, &a->dat)) return false;
     const size_t n = a->dat.s.size(), m = a->reg.s.size();
-    a->rows.resize(m * (size_t) a->width);
+    a->res.resize(m * (size_t) a->width);
     int rc;
-    if (prm_use_device()) {
+    if (wt_use_device((const void *) wtamd_runs_profile_host, "WTAMD_NO_DEVICE_PROFILE")) {
         rc = wtamd_runs_profile_host((int64_t) n, a->dat.s.data(), a->dat.f.data(), a->dat.v.data(), (int64_t) m, a->reg.s.data(), a->reg.f.data(),
-                                     (int32_t) a->width, dat->default_value, 0u, a->rows.data());
+                                     (int32_t) a->width, dat->default_value, 0u, a->res.data());
         if (rc != WTAMD_OK && rc != WTAMD_ERR_ARG) die("wtamd_runs_profile");
     } else {
         rc = wpr_profile_host((long long) n, a->dat.s.data(), a->dat.f.data(), a->dat.v.data(), (long long) m, a->reg.s.data(), a->reg.f.data(),
-                              (long long) a->width, dat->default_value, 0u, a->rows.data());
+                              (long long) a->width, dat->default_value, 0u, a->res.data());
     }
-    if (rc != 0) {
-        fprintf(stderr, "wiggletools_amd: wtamd_ProfileMultiplexer: on %s the dataset overlaps itself, or a side is not sorted by start or holds an "
-                        "interval with start >= finish; keep the reference's ProfileMultiplexer for such input\n", a->chrom);
-        exit(1);
-    }
+    if (rc != 0) rmx_refuse(a);
     return true;
 }
 
 void prm_pop(Multiplexer *m) {
-    ProfileMux *a = (ProfileMux *) m->data;
+    ProfileMux *a = (ProfileMux *) (RegionMux *) m->data;
     if (a->j >= a->reg.s.size() && !prm_load(a)) { m->done = 1; return; }
     m->chrom = (char *) a->chrom;
     m->start = a->reg.s[a->j]; m->finish = a->reg.f[a->j];
-    memcpy(m->values, a->rows.data() + a->j * (size_t) a->width, sizeof(double) * (size_t) a->width);
+    memcpy(m->values, a->res.data() + a->j * (size_t) a->width, sizeof(double) * (size_t) a->width);
     a->j++;
-}
-
-void prm_seek(Multiplexer *m, const char *chrom, int start, int finish) {
-    ProfileMux *a = (ProfileMux *) m->data;
-    seek(a->regions, chrom, start, finish);
-    seek(a->dataset, chrom, start, finish);
-    a->reg.clear(); a->dat.clear(); a->rows.clear();
-    a->j = 0;
-    m->done = 0;
-    prm_pop(m);
 }
 
 }  // namespace

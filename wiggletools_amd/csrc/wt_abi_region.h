@@ -4,8 +4,7 @@
 // commandParser.c:813-819) as ONE bulk source, wtamd_RegionIterator(op, source, mask).  It drains source and mask one
 // chromosome at a time (in blocks where the child is a bulk source of this library), pairs chromosomes by name in strcmp
 // order as the reference does, computes the chromosome's result through the device door (wtamd_runs_region, csrc/wt_region.hip)
-// and serves the finished run list -- to the library's Multiplexer in blocks, to wtamd_iterator_next_block, and to a foreign
-// pop() one run at a time.
+// and serves the finished run list as a ServedRuns (csrc/wt_abi_runs.h).
 //
 // The door is reached through a WEAK reference: a build of this layer without the HIP units (the emulated drop-in library of
 // the CPU tests) has no door and sweeps on the host by the same rules (csrc/wt_region.h), as does WTAMD_NO_DEVICE_REGION=1.
@@ -25,13 +24,6 @@ extern "C" int wtamd_runs_region_host(int op, int64_t n, const int32_t *start, c
                                       int32_t *o_finish, double *o_value, int64_t *n_out) __attribute__((weak));
 
 namespace {
-
-struct RegRuns {
-    std::vector<int32_t> s, f;
-    std::vector<double> v;
-    void clear() { s.clear(); f.clear(); v.clear(); }
-    void push(int32_t a, int32_t b, double x) { s.push_back(a); f.push_back(b); v.push_back(x); }
-};
 
 // the union of a mask sorted by start: an interval joins the group while group.finish > start (touching ones stay apart)
 void reg_union(const RegRuns &m, std::vector<int32_t> &gs, std::vector<int32_t> &gf) {
@@ -90,44 +82,12 @@ void reg_trim_protocol(const RegRuns &src, const RegRuns &mask, RegRuns &out) {
     }
 }
 
-struct RegIter {
-    BulkSource hdr;                 // must stay first (see wt_bulk_pop)
+struct RegIter : ServedRuns {      // (csrc/wt_abi_runs.h: BulkSource hdr stays first)
     int op = 0;
     WiggleIterator *source = nullptr, *mask = nullptr;
     Interner names;
-    const char *chrom = nullptr;    // interned name of the chromosome being served
-    RegRuns in, msk, out;
-    std::vector<float> vf;          // the values as float32 for the Multiplexer's blocks
-    int64_t j = 0;
-    bool done = false;
-    bool block_out = false;         // wtamd_iterator_next_block handed out [j, end): the next call moves past it
+    RegRuns in, msk;
 };
-
-bool reg_use_device() {
-    const char *e = getenv("WTAMD_NO_DEVICE_REGION");
-    return wtamd_runs_region_host != nullptr && !(e && atoi(e) != 0);
-}
-
-// Every interval of the chromosome `it` stands on, in blocks where it is a bulk source; keep == NULL: skipped.
-void reg_drain_chrom(WiggleIterator *it, const char *chrom, RegRuns *keep) {
-    BulkSource *bulk = it->pop == &wt_bulk_pop ? (BulkSource *) it->data : nullptr;
-    while (!it->done && strcmp(it->chrom, chrom) == 0) {
-        const int32_t *bs, *bf;
-        const float *bv;
-        const int64_t cnt = bulk ? bulk->peek(bulk, &bs, &bf, &bv) : 0;
-        if (cnt > 0) {
-            if (keep) {
-                keep->s.insert(keep->s.end(), bs, bs + cnt);
-                keep->f.insert(keep->f.end(), bf, bf + cnt);
-                keep->v.insert(keep->v.end(), bv, bv + cnt);
-            }
-            bulk->advance(bulk, it, cnt);
-        } else {
-            if (keep) keep->push(it->start, it->finish, it->value);
-            it->pop(it);
-        }
-    }
-}
 
 void reg_check_sorted(const RegRuns &r, const char *chrom, const char *side) {
     for (size_t q = 0; q < r.s.size(); q++)
@@ -138,10 +98,9 @@ void reg_check_sorted(const RegRuns &r, const char *chrom, const char *side) {
 }
 
 // Drains the next chromosome(s) of the source, with the mask's chromosome of the same name, until one has a result.
-void reg_load(RegIter *c) {
+void reg_load(ServedRuns *r) {
+    RegIter *c = (RegIter *) r;
     WiggleIterator *src = c->source, *mask = c->mask;
-    c->out.clear(); c->vf.clear();
-    c->j = 0;
     while (!src->done) {
         // the reference ends an overlaps / trim with its mask (unaryOps.c:456, :504)
         if (mask->done && (c->op == WTAMD_REGION_OVERLAPS || c->op == WTAMD_REGION_TRIM)) break;
@@ -160,7 +119,7 @@ void reg_load(RegIter *c) {
         for (size_t q = 1; q < n && disjoint; q++) disjoint = c->in.s[q] >= c->in.f[q - 1];
         if (c->op == WTAMD_REGION_TRIM && !disjoint) {
             reg_trim_protocol(c->in, c->msk, c->out);
-        } else if (reg_use_device()) {
+        } else if (wt_use_device((const void *) wtamd_runs_region_host, "WTAMD_NO_DEVICE_REGION")) {
             const int64_t cap = (int64_t) (c->op == WTAMD_REGION_TRIM ? n + m : n);
             c->out.s.resize((size_t) cap); c->out.f.resize((size_t) cap); c->out.v.resize((size_t) cap);
             int64_t n_out = 0;
@@ -171,61 +130,16 @@ void reg_load(RegIter *c) {
         } else {
             reg_host_sweep(c->op, c->in, c->msk, c->out);
         }
-        if (!c->out.s.empty()) {
-            c->vf.assign(c->out.v.begin(), c->out.v.end());
-            return;
-        }
+        if (!c->out.s.empty()) return;
     }
     c->done = true;
 }
 
-void reg_settle(RegIter *c, WiggleIterator *wi) {
-    if (!c->done && c->j >= (int64_t) c->out.s.size()) reg_load(c);
-    if (c->done) { wi->done = 1; return; }
-    wi->chrom = (char *) c->chrom;
-    wi->start = c->out.s[(size_t) c->j]; wi->finish = c->out.f[(size_t) c->j];
-    wi->value = c->out.v[(size_t) c->j];
-}
-
-int64_t reg_peek(BulkSource *b, const int32_t **s, const int32_t **f, const float **v) {
-    RegIter *c = (RegIter *) b;
-    if (c->done || c->block_out || c->j >= (int64_t) c->out.s.size()) return 0;
-    *s = c->out.s.data() + c->j; *f = c->out.f.data() + c->j; *v = c->vf.data() + c->j;
-    return (int64_t) c->out.s.size() - c->j;
-}
-
-void reg_advance(BulkSource *b, WiggleIterator *wi, int64_t k) {
-    RegIter *c = (RegIter *) b;
-    if (c->done) { wi->done = 1; return; }
-    if (c->block_out) { c->block_out = false; c->j = (int64_t) c->out.s.size(); }      // the block's runs have been taken
-    else c->j += k;
-    reg_settle(c, wi);
-}
-
 void reg_seek(WiggleIterator *wi, const char *chrom, int start, int finish) {
-    RegIter *c = (RegIter *) wi->data;
+    RegIter *c = (RegIter *) (ServedRuns *) wi->data;
     seek(c->source, chrom, start, finish);
     seek(c->mask, chrom, start, finish);
-    c->done = false;
-    c->block_out = false;
-    c->out.clear(); c->vf.clear();
-    c->j = 0;
-    wi->done = 0;
-    reg_settle(c, wi);
-}
-
-bool reg_is(WiggleIterator *wi) { return wi && wi->pop == &wt_bulk_pop && wi->data && ((BulkSource *) wi->data)->peek == &reg_peek; }
-
-// wtamd_iterator_next_block over a region iterator: the runs from the current element to the end of its chromosome
-int64_t reg_next_block(WiggleIterator *wi, const char **chrom, const int32_t **start, const int32_t **finish, const double **value) {
-    RegIter *c = (RegIter *) wi->data;
-    if (c->block_out) reg_advance(&c->hdr, wi, 0);
-    if (wi->done) return 0;
-    const int64_t n = (int64_t) c->out.s.size() - c->j;
-    if (chrom) *chrom = c->chrom;
-    *start = c->out.s.data() + c->j; *finish = c->out.f.data() + c->j; *value = c->out.v.data() + c->j;
-    c->block_out = true;
-    return n;
+    srv_restart(c, wi);
 }
 
 }  // namespace

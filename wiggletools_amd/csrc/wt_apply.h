@@ -330,39 +330,60 @@ WCV_DEV void wap_run_block(int kernel, const WapArgs &a, long long block, WapLds
 // ---------------------------------------------------------------------------------------------------------------------
 #ifndef WCV_NO_HOST
 
-template <class L>
-static int wap_apply(L &l, long long n_seg, const int64_t *seg_off, const int32_t *start, const int32_t *finish, const void *value,
-                     int value_is_f64, const int64_t *r_seg_off, const int32_t *r_start, const int32_t *r_finish, double default_value,
-                     unsigned int flags, double *moments6, const char **why) {
-    *why = "";
-    if (n_seg < 0 || !seg_off || !r_seg_off || n_seg >= (1ll << 31) || (flags & ~WAP_STRICT)) { *why = "bad argument"; return 1; }
-    if (n_seg && (seg_off[0] != 0 || r_seg_off[0] != 0)) { *why = "bad argument"; return 1; }
+// The opening of this door and of the one of wt_profile.h.  wap_open_check: the host's look at the segment offsets; a.n_seg,
+// a.start ... a.r_finish are set, a.n and a.n_r are set here; bad: what the door's own arguments (flags, width) already
+// refuse; out, out_always: the output is needed where there are regions, or always.  wap_open: d_seg / d_rseg on the device,
+// the scalars zeroed, the two validation passes -- valid(regions, blocks) launches the door's own instantiation -- and their
+// verdict.
+static int wap_open_check(WapArgs &a, const int64_t *seg_off, const int64_t *r_seg_off, bool bad, const void *out, bool out_always, const char **why) {
+    const long long n_seg = a.n_seg;
+    *why = "bad argument";
+    if (n_seg < 0 || !seg_off || !r_seg_off || n_seg >= (1ll << 31) || bad) return 1;
+    if (n_seg && (seg_off[0] != 0 || r_seg_off[0] != 0)) return 1;
     for (long long g = 0; g < n_seg; g++)
         if (seg_off[g + 1] < seg_off[g] || r_seg_off[g + 1] < r_seg_off[g]) { *why = "segment offsets decrease"; return 1; }
-    const long long n = n_seg ? (long long) seg_off[n_seg] : 0, n_r = n_seg ? (long long) r_seg_off[n_seg] : 0;
-    if ((n > 0 && (!start || !finish || !value)) || (n_r > 0 && (!r_start || !r_finish || !moments6))) { *why = "bad argument"; return 1; }
-    if (n >= (1ll << 31)) { *why = "more than 2^31 - 1 dataset runs"; return 1; }
-    WcvScope<L> sc(l);
-    WapArgs a = {};
-    a.n_seg = n_seg; a.n = n; a.n_r = n_r;
-    a.start = start; a.finish = finish; a.value = value; a.value_is_f64 = value_is_f64;
-    a.r_start = r_start; a.r_finish = r_finish;
-    a.default_value = default_value; a.flags = flags; a.out6 = moments6;
+    a.n = n_seg ? (long long) seg_off[n_seg] : 0; a.n_r = n_seg ? (long long) r_seg_off[n_seg] : 0;
+    if ((a.n > 0 && (!a.start || !a.finish || !a.value)) || (a.n_r > 0 && (!a.r_start || !a.r_finish)) || ((a.n_r > 0 || out_always) && !out)) return 1;
+    if (a.n >= (1ll << 31)) { *why = "more than 2^31 - 1 dataset runs"; return 1; }
+    *why = "";
+    return 0;
+}
+
+template <class L, class Valid>
+static int wap_open(L &l, WcvScope<L> &sc, WapArgs &a, const int64_t *seg_off, const int64_t *r_seg_off, Valid valid, const char **why) {
+    const size_t n_off = (size_t) a.n_seg + 1;
     int64_t *d_seg = nullptr, *d_rseg = nullptr;
-    if (!sc.get(&d_seg, (size_t) n_seg + 1) || !sc.get(&d_rseg, (size_t) n_seg + 1) || !sc.get(&a.scalars, (size_t) WAP_S_N))
-        { *why = "device memory"; return 2; }
-    if (!l.to_device(d_seg, seg_off, sizeof(int64_t) * ((size_t) n_seg + 1)) || !l.to_device(d_rseg, r_seg_off, sizeof(int64_t) * ((size_t) n_seg + 1)) ||
+    if (!sc.get(&d_seg, n_off) || !sc.get(&d_rseg, n_off) || !sc.get(&a.scalars, (size_t) WAP_S_N)) { *why = "device memory"; return 2; }
+    if (!l.to_device(d_seg, seg_off, sizeof(int64_t) * n_off) || !l.to_device(d_rseg, r_seg_off, sizeof(int64_t) * n_off) ||
         !l.zero(a.scalars, sizeof(long long) * WAP_S_N))
         { *why = "copy"; return 2; }
     a.seg_off = d_seg; a.r_seg_off = d_rseg;
     long long h_sc[WAP_S_N];
-    if (!l.run_apply(WAP_K_VALID_D, wcv_blocks(n, WAP_BLOCK), a) || !l.run_apply(WAP_K_VALID_R, wcv_blocks(n_r, WAP_BLOCK), a) ||
-        !l.to_host(h_sc, a.scalars, sizeof h_sc))
+    if (!valid(false, wcv_blocks(a.n, WAP_BLOCK)) || !valid(true, wcv_blocks(a.n_r, WAP_BLOCK)) || !l.to_host(h_sc, a.scalars, sizeof h_sc))
         { *why = "validation pass"; return 2; }
     if (h_sc[WAP_S_ERR]) {
         *why = "a segment is not sorted by start, holds an interval with start < 0 or start >= finish, or is a dataset that overlaps itself";
         return 1;
     }
+    return 0;
+}
+
+template <class L>
+static int wap_apply(L &l, long long n_seg, const int64_t *seg_off, const int32_t *start, const int32_t *finish, const void *value,
+                     int value_is_f64, const int64_t *r_seg_off, const int32_t *r_start, const int32_t *r_finish, double default_value,
+                     unsigned int flags, double *moments6, const char **why) {
+    WapArgs a = {};
+    a.n_seg = n_seg;
+    a.start = start; a.finish = finish; a.value = value; a.value_is_f64 = value_is_f64;
+    a.r_start = r_start; a.r_finish = r_finish;
+    a.default_value = default_value; a.flags = flags; a.out6 = moments6;
+    if (const int rc = wap_open_check(a, seg_off, r_seg_off, (flags & ~WAP_STRICT) != 0, moments6, false, why)) return rc;
+    const long long n_r = a.n_r;
+    WcvScope<L> sc(l);
+    if (const int rc = wap_open(l, sc, a, seg_off, r_seg_off,
+                                [&](bool regions, long long blocks) { return l.run_apply(regions ? WAP_K_VALID_R : WAP_K_VALID_D, blocks, a); }, why))
+        return rc;
+    long long h_sc[WAP_S_N];
     if (n_r == 0) return 0;
     a.tiles = wcv_blocks(n_r, WAP_TILE);
     if (!sc.get(&a.region, (size_t) n_r) || !sc.get(&a.tile_cnt, (size_t) a.tiles)) { *why = "device memory"; return 2; }

@@ -1,7 +1,8 @@
 // wt_apply.hip -- per-region statistics on the device: the six moments the reference's ApplyMultiplexer (src/apply.c; `apply`,
 // `apply_paste`) needs for AUC meanI varI stddevI CVI maxI minI of a dataset inside every region, over whole run lists in HBM.
 // The passes and the door are written once in csrc/wt_apply.h (which tests/apply_emu.cpp also compiles for the CPU); this
-// unit gives every pass its kernel and the door its launcher.  The scan of the tiles' chunk counts is a pass of
+// unit gives every pass its kernel; the launcher of the door, the report of its result and the staging of the *_host entry are
+// those of csrc/wt_runs_host.h.  The scan of the tiles' chunk counts is a pass of
 // csrc/wt_cover.h, launched by csrc/wt_cover.hip (wt_cover_run).  Temporary device memory comes from the pool (wt_pool.h).
 #include <hip/hip_runtime.h>
 
@@ -9,11 +10,8 @@
 #include <string>
 #include <vector>
 
-#include "wt_host.h"
-#include "wt_pool.h"
+#include "wt_runs_host.h"
 #include "wt_apply.h"
-
-bool wt_cover_run(void *stream, int kernel, long long blocks, const WcvArgs &a);      // csrc/wt_cover.hip
 
 namespace {
 
@@ -23,34 +21,8 @@ __global__ void __launch_bounds__(WAP_BLOCK) wt_apply_kernel(WapArgs a) {
     wap_run_block(K, a, (long long) blockIdx.x, &lds);
 }
 
-struct HipApplyLauncher {
-    hipStream_t s;
-    bool quiet = false;         // nothing has been put on `s` since it was last waited for, and only `s` touches the buffers: they may
-                                // return to the pool without the device-wide wait
-    void *alloc(size_t bytes) {
-        void *p = nullptr;
-        return wt_dev_alloc_bytes(&p, bytes, __FILE__, __LINE__) == hipSuccess ? p : nullptr;
-    }
-    void release(void *p) {
-        if (!quiet) { (void) wt_pool_quiesce(); quiet = true; }
-        (void) wt_dev_free(p);
-    }
-    bool zero(void *p, size_t bytes) { quiet = false; return hipMemsetAsync(p, 0, bytes, s) == hipSuccess; }
-    bool sync() { return quiet = hipStreamSynchronize(s) == hipSuccess; }
-    bool to_host(void *h, const void *d, size_t bytes) {
-        return hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, s) == hipSuccess && sync();
-    }
-    bool to_device(void *d, const void *h, size_t bytes) {
-        return hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s) == hipSuccess && sync();
-    }
-    bool run(int kernel, long long blocks, const WcvArgs &a) { quiet = false; return wt_cover_run((void *) s, kernel, blocks, a); }
-    template <int K> bool launch(long long blocks, const WapArgs &a) {
-        if (blocks <= 0) return true;
-        if (blocks > 0x7fffffffll) return false;
-        quiet = false;
-        hipLaunchKernelGGL(wt_apply_kernel<K>, dim3((unsigned) blocks), dim3(WAP_BLOCK), 0, s, a);
-        return hipGetLastError() == hipSuccess;
-    }
+struct HipApplyLauncher : WtRunsLauncher {
+    template <int K> bool launch(long long blocks, const WapArgs &a) { return WtRunsLauncher::launch(wt_apply_kernel<K>, WAP_BLOCK, blocks, a); }
     bool run_apply(int kernel, long long blocks, const WapArgs &a) {
         switch (kernel) {
         case WAP_K_VALID_D: return launch<WAP_K_VALID_D>(blocks, a);
@@ -72,14 +44,11 @@ int wtamd_runs_apply(int64_t n_seg, const int64_t *seg_off, const int32_t *start
                      double *moments6, void *stream) {
     static_assert(WAP_STRICT == WTAMD_APPLY_STRICT, "wt_apply.h and wiggletools_amd.h name the flag alike");
     static_assert(sizeof(WapRegion) == 16 && sizeof(WapPartial) == 64, "the scratch figures of the header");
-    HipApplyLauncher l{(hipStream_t) stream};
+    HipApplyLauncher l{{(hipStream_t) stream, __FILE__}};
     const char *why = "";
     const int rc = wap_apply(l, (long long) n_seg, seg_off, start, finish, value, value_is_f64, r_seg_off, r_start, r_finish, default_value,
                              (unsigned int) flags, moments6, &why);
-    if (rc == 0) return WTAMD_OK;
-    if (rc == 1) return wt_fail(WTAMD_ERR_ARG, std::string("wtamd_runs_apply: ") + why);
-    const hipError_t e = hipGetLastError();
-    return wt_fail(WTAMD_ERR_HIP, std::string("wtamd_runs_apply: ") + why + " (" + hipGetErrorString(e) + ")");
+    return wt_runs_report("wtamd_runs_apply", rc, why);
 }
 
 // One segment pair in HOST memory in, 6 doubles per region in HOST memory out: device memory from the pool, copies and the
@@ -88,24 +57,15 @@ int wtamd_runs_apply_host(int64_t n, const int32_t *start, const int32_t *finish
                           const int32_t *r_start, const int32_t *r_finish, double default_value, uint32_t flags, double *moments6) {
     if (n < 0 || n_regions < 0 || (n > 0 && (!start || !finish || !value)) || (n_regions > 0 && (!r_start || !r_finish || !moments6)))
         return wt_fail(WTAMD_ERR_ARG, "wtamd_runs_apply_host: bad argument");
-    HipApplyLauncher l{nullptr};
+    HipApplyLauncher l{{nullptr, __FILE__}};
     WcvScope<HipApplyLauncher> sc(l);
-    int32_t *d_in = nullptr, *d_reg = nullptr;
-    double *d_val = nullptr, *d_out = nullptr;
-    const size_t n1 = (size_t) (n > 0 ? n : 1), r1 = (size_t) (n_regions > 0 ? n_regions : 1);
-    if (!sc.get(&d_in, 2 * n1) || !sc.get(&d_val, n1) || !sc.get(&d_reg, 2 * r1) || !sc.get(&d_out, 6 * r1))
-        return wt_fail(WTAMD_ERR_HIP, "wtamd_runs_apply_host: out of device memory");
-    if (n > 0) {
-        WT_HIP(hipMemcpy(d_in, start, sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice));
-        WT_HIP(hipMemcpy(d_in + n1, finish, sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice));
-        WT_HIP(hipMemcpy(d_val, value, sizeof(double) * (size_t) n, hipMemcpyHostToDevice));
-    }
-    if (n_regions > 0) {
-        WT_HIP(hipMemcpy(d_reg, r_start, sizeof(int32_t) * (size_t) n_regions, hipMemcpyHostToDevice));
-        WT_HIP(hipMemcpy(d_reg + r1, r_finish, sizeof(int32_t) * (size_t) n_regions, hipMemcpyHostToDevice));
-    }
+    WtDevRuns in, reg;
+    double *d_out = nullptr;
+    if (const int e = wt_stage_runs("wtamd_runs_apply_host", sc, n, start, finish, value, true, &in)) return e;
+    if (const int e = wt_stage_runs("wtamd_runs_apply_host", sc, n_regions, r_start, r_finish, nullptr, false, &reg)) return e;
+    if (!sc.get(&d_out, 6 * (size_t) (n_regions > 0 ? n_regions : 1))) return wt_fail(WTAMD_ERR_HIP, "wtamd_runs_apply_host: out of device memory");
     const int64_t seg[2] = {0, n}, rseg[2] = {0, n_regions};
-    const int rc = wtamd_runs_apply(1, seg, d_in, d_in + n1, d_val, 1, rseg, d_reg, d_reg + r1, default_value, flags, d_out, nullptr);
+    const int rc = wtamd_runs_apply(1, seg, in.start, in.finish, in.value, 1, rseg, reg.start, reg.finish, default_value, flags, d_out, nullptr);
     if (rc != WTAMD_OK) return rc;
     if (n_regions > 0) WT_HIP(hipMemcpy(moments6, d_out, sizeof(double) * 6 * (size_t) n_regions, hipMemcpyDeviceToHost));
     l.quiet = true;             // (the call waited for its stream and the copy home for the device: the buffers are idle)

@@ -540,7 +540,7 @@ WCV_DEV void wcv_run_block(int kernel, const WcvArgs &a, long long block, WcvLds
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// The two doors, written once over a Launcher (the device: csrc/wt_cover.hip; the CPU: tests/cover_emu.cpp):
+// The two doors, written once over a Launcher (the device: csrc/wt_runs_host.h; the CPU: tests/emu/runs_launcher.h):
 //   void *alloc(size_t bytes)                 device memory, NULL on failure       void release(void *)
 //   bool zero(void *p, size_t bytes)          bool to_host(void *h, const void *d, size_t)  (waits)
 //   bool to_device(void *d, const void *h, size_t)

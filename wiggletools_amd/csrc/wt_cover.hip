@@ -1,7 +1,8 @@
 // wt_cover.hip -- coverage and union of overlapping intervals on the device: the reference's CoverageWiggleIterator
 // (src/unaryOps.c:303-375, the `coverage` command) and UnionWiggleIterator (:60-92) over whole run lists in HBM.  The passes
 // and the two doors are written once in csrc/wt_cover.h (which tests/cover_emu.cpp also compiles for the CPU); this unit
-// gives every pass its kernel and the doors their launcher.
+// gives every pass its kernel; the launcher of the doors, the report of their result and the staging of the *_host entry are
+// those of csrc/wt_runs_host.h, with memory from hipMalloc.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -9,8 +10,7 @@
 #include <string>
 #include <vector>
 
-#include "wt_host.h"
-#include "wt_cover.h"
+#include "wt_runs_host.h"
 
 namespace {
 
@@ -20,27 +20,8 @@ __global__ void __launch_bounds__(WCV_BLOCK) wt_cover_kernel(WcvArgs a) {
     wcv_run_block(K, a, (long long) blockIdx.x, &lds);
 }
 
-struct HipLauncher {
-    hipStream_t s;
-    void *alloc(size_t bytes) {
-        void *p = nullptr;
-        return hipMalloc(&p, bytes) == hipSuccess ? p : nullptr;
-    }
-    void release(void *p) { (void) hipFree(p); }
-    bool zero(void *p, size_t bytes) { return hipMemsetAsync(p, 0, bytes, s) == hipSuccess; }
-    bool to_host(void *h, const void *d, size_t bytes) {
-        return hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
-    }
-    bool to_device(void *d, const void *h, size_t bytes) {
-        // (the host tables are reused by the caller: the copy has left them when this returns)
-        return hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
-    }
-    template <int K> bool launch(long long blocks, const WcvArgs &a) {
-        if (blocks <= 0) return true;
-        if (blocks > 0x7fffffffll) return false;
-        hipLaunchKernelGGL(wt_cover_kernel<K>, dim3((unsigned) blocks), dim3(WCV_BLOCK), 0, s, a);
-        return hipGetLastError() == hipSuccess;
-    }
+struct HipLauncher : WtRunsLauncher {
+    template <int K> bool launch(long long blocks, const WcvArgs &a) { return WtRunsLauncher::launch(wt_cover_kernel<K>, WCV_BLOCK, blocks, a); }
     bool run(int kernel, long long blocks, const WcvArgs &a) {
         switch (kernel) {
         case WCV_K_PRE: return launch<WCV_K_PRE>(blocks, a);
@@ -62,14 +43,6 @@ struct HipLauncher {
     }
 };
 
-int wcv_report(const char *door, int rc, const char *why) {
-    if (rc == 0) return WTAMD_OK;
-    if (rc == 3) return wt_fail(WTAMD_ERR_CAPACITY, std::string(door) + ": the output arrays are too small (*n_out holds the count needed)");
-    if (rc == 1) return wt_fail(WTAMD_ERR_ARG, std::string(door) + ": " + why);
-    const hipError_t e = hipGetLastError();
-    return wt_fail(WTAMD_ERR_HIP, std::string(door) + ": " + why + " (" + hipGetErrorString(e) + ")");
-}
-
 long long wcv_budget() {
     const char *e = getenv("WTAMD_COVER_SCRATCH_MB");
     const long long mb = e && atoll(e) > 0 ? atoll(e) : 256;
@@ -80,7 +53,7 @@ long long wcv_budget() {
 
 // one pass of wt_cover.h on a stream, for the other units that use them (csrc/wt_region.hip: the union of a mask, the scan)
 bool wt_cover_run(void *stream, int kernel, long long blocks, const WcvArgs &a) {
-    HipLauncher l{(hipStream_t) stream};
+    HipLauncher l{{(hipStream_t) stream, nullptr}};
     return l.run(kernel, blocks, a);
 }
 
@@ -88,21 +61,21 @@ extern "C" {
 
 int wtamd_runs_coverage(int64_t n_seg, const int64_t *seg_off, const int32_t *start, const int32_t *finish, int64_t capacity,
                         int32_t *o_start, int32_t *o_finish, double *o_value, int64_t *o_seg_off, int64_t *n_out, void *stream) {
-    HipLauncher l{(hipStream_t) stream};
+    HipLauncher l{{(hipStream_t) stream, nullptr}};
     const char *why = "";
     const int rc = wcv_coverage(l, (long long) n_seg, seg_off, start, finish, (long long) capacity, o_start, o_finish, o_value, o_seg_off,
                                 n_out, wcv_budget(), &why);
-    return wcv_report("wtamd_runs_coverage", rc, why);
+    return wt_runs_report("wtamd_runs_coverage", rc, why);
 }
 
 int wtamd_runs_union(int64_t n_seg, const int64_t *seg_off, const int32_t *start, const int32_t *finish, const void *value,
                      int value_is_f64, int64_t capacity, int32_t *o_start, int32_t *o_finish, double *o_value, int64_t *o_seg_off,
                      int64_t *n_out, void *stream) {
-    HipLauncher l{(hipStream_t) stream};
+    HipLauncher l{{(hipStream_t) stream, nullptr}};
     const char *why = "";
     const int rc = wcv_union(l, (long long) n_seg, seg_off, start, finish, value, value_is_f64, (long long) capacity, o_start, o_finish,
                              o_value, o_seg_off, n_out, &why);
-    return wcv_report("wtamd_runs_union", rc, why);
+    return wt_runs_report("wtamd_runs_union", rc, why);
 }
 
 // One segment in HOST memory in, its depth track in HOST memory out (what wtamd_CoverageIterator calls per chromosome).
@@ -112,19 +85,17 @@ int wtamd_runs_coverage_host(int64_t n, const int32_t *start, const int32_t *fin
     *n_out = 0;
     if (n == 0) return WTAMD_OK;
     const int64_t cap = 2 * n - 1;
-    int32_t *d_in = nullptr, *d_out = nullptr;
+    HipLauncher l{{nullptr, nullptr}};
+    WcvScope<HipLauncher> sc(l);
+    WtDevRuns in;
+    int32_t *d_out = nullptr;
     double *d_val = nullptr;
-    WT_HIP(hipMalloc(&d_in, sizeof(int32_t) * 2 * (size_t) n));
-    struct Free { void *p; ~Free() { (void) hipFree(p); } } f1{d_in};
-    WT_HIP(hipMalloc(&d_out, sizeof(int32_t) * 2 * (size_t) cap));
-    Free f2{d_out};
-    WT_HIP(hipMalloc(&d_val, sizeof(double) * (size_t) cap));
-    Free f3{d_val};
-    WT_HIP(hipMemcpy(d_in, start, sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice));
-    WT_HIP(hipMemcpy(d_in + n, finish, sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice));
+    if (const int e = wt_stage_runs("wtamd_runs_coverage_host", sc, n, start, finish, nullptr, false, &in)) return e;
+    if (!sc.get(&d_out, 2 * (size_t) cap) || !sc.get(&d_val, (size_t) cap))
+        return wt_fail(WTAMD_ERR_HIP, "wtamd_runs_coverage_host: out of device memory");
     const int64_t seg[2] = {0, n};
     int64_t oseg[2] = {0, 0};
-    const int rc = wtamd_runs_coverage(1, seg, d_in, d_in + n, cap, d_out, d_out + cap, d_val, oseg, n_out, nullptr);
+    const int rc = wtamd_runs_coverage(1, seg, in.start, in.finish, cap, d_out, d_out + cap, d_val, oseg, n_out, nullptr);
     if (rc != WTAMD_OK) return rc;
     if (*n_out > capacity) return wt_fail(WTAMD_ERR_CAPACITY, "wtamd_runs_coverage_host: the output arrays are too small (*n_out holds the count needed)");
     if (*n_out > 0) {

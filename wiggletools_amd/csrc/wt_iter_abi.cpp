@@ -128,6 +128,7 @@ void wt_bulk_pop(WiggleIterator *wi) {
 #include "wt_abi_feeder.h"
 #include "wt_abi_reduce.h"
 #include "wt_abi_readers.h"
+#include "wt_abi_runs.h"
 #include "wt_abi_cover.h"
 #include "wt_abi_region.h"
 #include "wt_abi_apply.h"
@@ -488,19 +489,9 @@ WiggleIterator *wtamd_OverlappingArrayReader(int n_chrom, const char *const *chr
 WiggleIterator *wtamd_CoverageIterator(WiggleIterator *child) {
     if (!child->overlaps) return child;
     CovIter *c = new (calloc(1, sizeof(CovIter))) CovIter();
-    c->hdr.peek = &cov_peek;
-    c->hdr.advance = &cov_advance;
-    c->hdr.stable = false;                     // the run list is replaced chromosome by chromosome
+    c->load = &cov_load;
     c->child = child;
-    WiggleIterator *wi = (WiggleIterator *) calloc(1, sizeof(WiggleIterator));
-    wi->data = c;
-    wi->pop = &wt_bulk_pop;
-    wi->seek = &cov_seek;
-    wi->value = 1;
-    wi->overlaps = 0;
-    wi->default_value = 0;                     // :372
-    cov_settle(c, wi);                         // a fresh iterator already holds its first element (wiggleIterator.c:32)
-    return wi;
+    return srv_iterator(c, &cov_seek, 0, 0);   // default value: :372
 }
 
 // Overlap / Noverlap / Trim / NearestWiggleIterator (unaryOps.c:437-639) on the device door
@@ -510,21 +501,11 @@ WiggleIterator *wtamd_RegionIterator(int op, WiggleIterator *source, WiggleItera
         exit(1);
     }
     RegIter *c = new (calloc(1, sizeof(RegIter))) RegIter();
-    c->hdr.peek = &reg_peek;
-    c->hdr.advance = &reg_advance;
-    c->hdr.stable = false;                     // the run list is replaced chromosome by chromosome
+    c->load = &reg_load;
     c->op = op;
     c->source = source;
     c->mask = mask;
-    WiggleIterator *wi = (WiggleIterator *) calloc(1, sizeof(WiggleIterator));
-    wi->data = c;
-    wi->pop = &wt_bulk_pop;
-    wi->seek = &reg_seek;
-    wi->value = 1;
-    wi->overlaps = source->overlaps;           // :478
-    wi->default_value = source->default_value;
-    reg_settle(c, wi);                         // a fresh iterator already holds its first element (wiggleIterator.c:32)
-    return wi;
+    return srv_iterator(c, &reg_seek, source->overlaps, source->default_value);        // :478
 }
 
 // ApplyMultiplexer (apply.c:341-353) on the device door: primed with the first region, done after the last
@@ -541,7 +522,7 @@ Multiplexer *wtamd_ApplyMultiplexer(WiggleIterator *regions, const int *stats, i
     ApplyMux *a = new ApplyMux();
     a->regions = regions; a->dataset = dataset; a->strict = strict != 0;
     a->stats.assign(stats, stats + count);
-    Multiplexer *m = newCoreMultiplexer(a, count, &apm_pop, &apm_seek);
+    Multiplexer *m = newCoreMultiplexer((RegionMux *) a, count, &apm_pop, &rmx_seek);
     m->strict = strict;
     for (int i = 0; i < count; i++) m->default_values[i] = NAN;     // apply.c:349-350
     popMultiplexer(m);
@@ -560,7 +541,7 @@ Multiplexer *wtamd_ProfileMultiplexer(WiggleIterator *regions, int width, Wiggle
     }
     ProfileMux *a = new ProfileMux();
     a->regions = regions; a->dataset = dataset; a->width = width;
-    Multiplexer *m = newCoreMultiplexer(a, width, &prm_pop, &prm_seek);
+    Multiplexer *m = newCoreMultiplexer((RegionMux *) a, width, &prm_pop, &rmx_seek);
     m->strict = 0;                                                  // apply.c:359
     for (int i = 0; i < width; i++) m->default_values[i] = NAN;     // apply.c:362-363
     popMultiplexer(m);
@@ -569,8 +550,7 @@ Multiplexer *wtamd_ProfileMultiplexer(WiggleIterator *regions, int width, Wiggle
 
 int64_t wtamd_iterator_next_block(WiggleIterator *wi, const char **chrom, const int32_t **start,
                                   const int32_t **finish, const double **value) {
-    if (cov_is(wi)) return cov_next_block(wi, chrom, start, finish, value);     // a coverage iterator: to the end of its chromosome
-    if (reg_is(wi)) return reg_next_block(wi, chrom, start, finish, value);     // a region iterator likewise
+    if (srv_is(wi)) return srv_next_block(wi, chrom, start, finish, value);     // a coverage or region iterator: to the end of its chromosome
     if (!wi || wi->pop != &red_pop) return -1;          // otherwise reducers of this library only
     RedState *R = red_state(wi);
     if (R->block_done) red_pop(wi);                     // the previous block emptied its batch: fetch the next

@@ -338,39 +338,22 @@ template <class L>
 static int wpr_profile(L &l, long long n_seg, const int64_t *seg_off, const int32_t *start, const int32_t *finish, const void *value,
                        int value_is_f64, const int64_t *r_seg_off, const int32_t *r_start, const int32_t *r_finish, long long width,
                        double default_value, unsigned int flags, long long batch, double *profile, const char **why) {
-    *why = "";
-    if (n_seg < 0 || !seg_off || !r_seg_off || n_seg >= (1ll << 31) || (flags & ~WPR_SUM) || width < 1 || width >= (1ll << 31) || batch < 0)
-        { *why = "bad argument"; return 1; }
-    if (n_seg && (seg_off[0] != 0 || r_seg_off[0] != 0)) { *why = "bad argument"; return 1; }
-    for (long long g = 0; g < n_seg; g++)
-        if (seg_off[g + 1] < seg_off[g] || r_seg_off[g + 1] < r_seg_off[g]) { *why = "segment offsets decrease"; return 1; }
-    const long long n = n_seg ? (long long) seg_off[n_seg] : 0, n_r = n_seg ? (long long) r_seg_off[n_seg] : 0;
     const bool sum = (flags & WPR_SUM) != 0;
-    if ((n > 0 && (!start || !finish || !value)) || (n_r > 0 && (!r_start || !r_finish)) || ((n_r > 0 || sum) && !profile)) { *why = "bad argument"; return 1; }
-    if (n >= (1ll << 31)) { *why = "more than 2^31 - 1 dataset runs"; return 1; }
-    if (n_r >= (1ll << 31)) { *why = "more than 2^31 - 1 regions"; return 1; }
-    WcvScope<L> sc(l);
     WprArgs a = {};
     a.width = width;
-    a.ap.n_seg = n_seg; a.ap.n = n; a.ap.n_r = n_r;
+    a.ap.n_seg = n_seg;
     a.ap.start = start; a.ap.finish = finish; a.ap.value = value; a.ap.value_is_f64 = value_is_f64;
     a.ap.r_start = r_start; a.ap.r_finish = r_finish;
     a.ap.default_value = default_value;
-    int64_t *d_seg = nullptr, *d_rseg = nullptr;
-    if (!sc.get(&d_seg, (size_t) n_seg + 1) || !sc.get(&d_rseg, (size_t) n_seg + 1) || !sc.get(&a.ap.scalars, (size_t) WPR_S_N))
-        { *why = "device memory"; return 2; }
-    if (!l.to_device(d_seg, seg_off, sizeof(int64_t) * ((size_t) n_seg + 1)) || !l.to_device(d_rseg, r_seg_off, sizeof(int64_t) * ((size_t) n_seg + 1)) ||
-        !l.zero(a.ap.scalars, sizeof(long long) * WPR_S_N))
-        { *why = "copy"; return 2; }
-    a.ap.seg_off = d_seg; a.ap.r_seg_off = d_rseg;
+    if (const int rc = wap_open_check(a.ap, seg_off, r_seg_off, (flags & ~WPR_SUM) || width < 1 || width >= (1ll << 31) || batch < 0, profile, sum, why))
+        return rc;
+    const long long n_r = a.ap.n_r;
+    if (n_r >= (1ll << 31)) { *why = "more than 2^31 - 1 regions"; return 1; }
+    WcvScope<L> sc(l);
+    if (const int rc = wap_open(l, sc, a.ap, seg_off, r_seg_off,
+                                [&](bool regions, long long blocks) { return l.run_profile(regions ? WPR_K_VALID_R : WPR_K_VALID_D, blocks, a); }, why))
+        return rc;
     long long h_sc[WPR_S_N];
-    if (!l.run_profile(WPR_K_VALID_D, wcv_blocks(n, WPR_BLOCK), a) || !l.run_profile(WPR_K_VALID_R, wcv_blocks(n_r, WPR_BLOCK), a) ||
-        !l.to_host(h_sc, a.ap.scalars, sizeof h_sc))
-        { *why = "validation pass"; return 2; }
-    if (h_sc[WPR_S_ERR]) {
-        *why = "a segment is not sorted by start, holds an interval with start < 0 or start >= finish, or is a dataset that overlaps itself";
-        return 1;
-    }
     if (n_r == 0) {
         if (sum && (!l.zero(profile, sizeof(double) * (size_t) width) || !l.sync())) { *why = "copy"; return 2; }
         return 0;
