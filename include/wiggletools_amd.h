@@ -551,6 +551,49 @@ int wtamd_runs_profile_host(int64_t n, const int32_t *start, const int32_t *fini
                             int64_t n_regions, const int32_t *r_start, const int32_t *r_finish,
                             int32_t width, double default_value, uint32_t flags, double *profile);
 
+/* The window operators on device (csrc/wt_window.hip): the reference's BinningWiggleIterator (src/unaryOps.c:963-1036; the
+ * parser's `bin`) and SmoothWiggleIterator (:1039-1162; `smooth`) over whole run lists.  The layout of wtamd_runs_map: n_seg
+ * segments, seg_off / o_seg_off HOST arrays of n_seg + 1 offsets, start / finish / value (f32 or f64) DEVICE arrays; outputs
+ * o_start / o_finish / o_value (f64) DEVICE arrays of `capacity` entries, *n_out on the host.  Inside a segment the runs are
+ * sorted, start < finish, DISJOINT (the reference puts its union in front of both operators) and start >= 1; fewer than 2^31 runs.
+ * WTAMD_ERR_CAPACITY: *n_out holds the count needed, nothing written.  WTAMD_ERR_ARG, nothing written: width < 2, a segment
+ * that breaks those rules, or an output coordinate that would pass INT32_MAX.
+ * BIN, width w.  The grid bins of a segment are [1 + k w, 1 + (k + 1) w); a bin is emitted, in order, if and only if a run
+ * intersects it (the reference's "continue at the last finish" and "realign" rules land on the same grid); adjacent bins are
+ * not merged.  A bin's value starts at 0.0 and takes (double) (int) covered * value of every intersecting run in order; then,
+ * if default_value is not zero -- NaN counts as not zero, the reference tests `if (iter->default_value && ...)` -- and the
+ * covered length is below w, (w - covered) * default_value.  An all -0.0 bin gives +0.0.  The default of the result is
+ * default_value * w.  The output count is at most the sum over the runs of the bins each touches.  A bin with more than 32
+ * runs under it is summed as 64 contiguous shares merged pairwise, lower share first, the default's term last.
+ * SMOOTH, width w, h = w / 2.  One run [p, p + 1) per position; every segment is ONE island.  With s the first start and F the
+ * last finish: it starts at p0 = max(1, s - h), after a prefill that reads positions 1 .. h when s - h < 1; the value at p is
+ * (sum of the buffer) / w, the buffer holding the last <= w positions read up to p + h.  A position inside the segment that no
+ * run covers reads as 0, NOT as the default.  Nothing is read from position F on (even when it is asked for during the
+ * prefill); from then on every pop drops exactly one value, the oldest, and the island ends when none is left -- so a
+ * chromosome shorter than w shrinks from its first read position, not by the window formula.  A window holding a NaN gives NaN;
+ * once the NaN has left, the sum is that of the remaining values (the NaN positions are counted apart from the sum).  Zero
+ * sums are +0.0.  The default of the result is the child's.  The output count is at most (F - p0) + w per segment, 16 bytes
+ * per position: [clip_lo, clip_hi) restricts the positions DELIVERED, in every segment (0, 0: no clip), and the bits of a
+ * position do not depend on it.  The sum of a position is formed over a strip of 16 outputs aligned to p0: the first window
+ * from the runs under it as len * value in run order, the following ones by adding the value that enters and subtracting the
+ * one that leaves -- the reference's running sum carries its whole history instead, so values that are not exact sums differ
+ * from it by rounding (within (m + 2) 2^-53 x the largest window sum of |values| / w, m <= runs under a window + 30).
+ * The bits of either result depend only on the segment's runs, the width and the default.  Synchronous on `stream`; temporary
+ * memory from the device pool: bin 8 bytes per run + 40 bytes per 256 output bins, smooth 96 bytes per segment. */
+int wtamd_runs_bin(int64_t n_seg, const int64_t *seg_off, const int32_t *start, const int32_t *finish, const void *value, int value_is_f64,
+                   int32_t width, double default_value,
+                   int64_t capacity, int32_t *o_start, int32_t *o_finish, double *o_value, int64_t *o_seg_off, int64_t *n_out, void *stream);
+int wtamd_runs_smooth(int64_t n_seg, const int64_t *seg_off, const int32_t *start, const int32_t *finish, const void *value, int value_is_f64,
+                      int32_t width, int32_t clip_lo, int32_t clip_hi,
+                      int64_t capacity, int32_t *o_start, int32_t *o_finish, double *o_value, int64_t *o_seg_off, int64_t *n_out, void *stream);
+/* Either door over ONE segment held in HOST arrays, result in HOST arrays (what wtamd_BinIterator / wtamd_SmoothIterator call
+ * per chromosome, smooth per clip slice): device memory, copies and the call on the null stream. */
+int wtamd_runs_bin_host(int64_t n, const int32_t *start, const int32_t *finish, const double *value, int32_t width, double default_value,
+                        int64_t capacity, int32_t *o_start, int32_t *o_finish, double *o_value, int64_t *n_out);
+int wtamd_runs_smooth_host(int64_t n, const int32_t *start, const int32_t *finish, const double *value, int32_t width,
+                           int32_t clip_lo, int32_t clip_hi,
+                           int64_t capacity, int32_t *o_start, int32_t *o_finish, double *o_value, int64_t *n_out);
+
 /* Run compression on device (reference CompressionWiggleIterator, unaryOps.c:235-253, which the
  * default writer applies, wigWriter.c:263-267): adjacent runs of one chromosome merge while
  * start == previous finish and (both NaN or |value - value of the group's first run| < 1e-6).
@@ -801,6 +844,18 @@ Multiplexer *wtamd_ApplyMultiplexer(WiggleIterator *regions, const int *stats, i
  * Refused with a message and exit(1): width < 1, a dataset with `overlaps` set or one that is not disjoint, regions that are not
  * sorted.  The departures listed at wtamd_runs_profile hold. */
 Multiplexer *wtamd_ProfileMultiplexer(WiggleIterator *regions, int width, WiggleIterator *dataset);
+/* The reference's BinningWiggleIterator (unaryOps.c:1027-1036; `bin`) and SmoothWiggleIterator (:1152-1162; `smooth`) on
+ * wtamd_runs_bin / wtamd_runs_smooth: they drain the child one chromosome at a time (in blocks where it is a bulk source), put
+ * the union in front when child->overlaps, compute the chromosome through the device door and serve the finished run list --
+ * smooth in clip slices of 2^20 positions (WTAMD_WINDOW_SLICE=<n>: of n), so a chromosome never needs 16 bytes per base pair of host memory at once.  Bulk
+ * sources themselves (a Multiplexer of this library and wtamd_iterator_next_block take them in blocks).  Defaults: child's x
+ * width, child's.  seek seeks the child and recomputes.  WTAMD_NO_DEVICE_WINDOW=1 (or a build of the drop-in layer without the
+ * HIP units) computes the same bits with a host sweep.  A chromosome with a start below 1 is served by the reference's own
+ * per-pop protocol on the host (C's division towards zero, the prefill from position 1).  A width below 2: the reference's
+ * message and exit(1).  A child that is not sorted, or overlaps without saying so: a message and exit(1).  Unlike the
+ * reference's smooth, whose running sum carries over from one chromosome to the next, every chromosome starts from 0. */
+WiggleIterator *wtamd_BinIterator(WiggleIterator *child, int width);
+WiggleIterator *wtamd_SmoothIterator(WiggleIterator *child, int width);
 /* BigWig reader: the role of the reference's BigWiggleReader (src/bigWiggleReader.c:147-151) on this
  * library's own section decoder -- chromosomes in strcmp order, 1-based starts, box != 0: intervals
  * cut at the reference reader's 10 000-bp stretch edges (what `write_bg` parity needs); one producer

@@ -133,6 +133,7 @@ void wt_bulk_pop(WiggleIterator *wi) {
 #include "wt_abi_region.h"
 #include "wt_abi_apply.h"
 #include "wt_abi_profile.h"
+#include "wt_abi_window.h"
 #include "wt_abi_bwdev.h"
 #include "wt_abi_ops.h"
 #include "wt_abi_integrators.h"
@@ -547,6 +548,10 @@ Multiplexer *wtamd_ProfileMultiplexer(WiggleIterator *regions, int width, Wiggle
     popMultiplexer(m);
     return m;
 }
+
+// BinningWiggleIterator (unaryOps.c:1027-1036) and SmoothWiggleIterator (:1152-1162) on the device doors
+WiggleIterator *wtamd_BinIterator(WiggleIterator *child, int width) { return win_iterator(child, width, false); }
+WiggleIterator *wtamd_SmoothIterator(WiggleIterator *child, int width) { return win_iterator(child, width, true); }
 
 int64_t wtamd_iterator_next_block(WiggleIterator *wi, const char **chrom, const int32_t **start,
                                   const int32_t **finish, const double **value) {

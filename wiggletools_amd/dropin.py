@@ -133,6 +133,24 @@ def profile_multiplexer(regions, width, dataset):
     return L.wtamd_ProfileMultiplexer(regions, int(width), dataset)
 
 
+def bin_iterator(child, width):
+    """wtamd_BinIterator: the reference's `bin` of `child` over windows of `width` base pairs on the grid from position 1; a bulk
+    source for multiplexer() / reducer(), readable with drain_blocks() and drain_pops()."""
+    L = _bind()
+    L.wtamd_BinIterator.restype = C.c_void_p
+    L.wtamd_BinIterator.argtypes = [C.c_void_p, C.c_int]
+    return L.wtamd_BinIterator(child, int(width))
+
+
+def smooth_iterator(child, width):
+    """wtamd_SmoothIterator: the reference's `smooth` of `child`, one run per position with the mean of `width` positions around
+    it; a bulk source for multiplexer() / reducer(), readable with drain_blocks() and drain_pops()."""
+    L = _bind()
+    L.wtamd_SmoothIterator.restype = C.c_void_p
+    L.wtamd_SmoothIterator.argtypes = [C.c_void_p, C.c_int]
+    return L.wtamd_SmoothIterator(child, int(width))
+
+
 def bigwig_reader(path, box=True):
     """wtamd_BigWiggleReader: the reference's BigWiggleReader role (bigWiggleReader.c:147-151), bulk-capable."""
     return _bind().wtamd_BigWiggleReader(path.encode(), int(box))

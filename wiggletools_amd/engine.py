@@ -234,6 +234,70 @@ def profile_runlists(data: RunLists, regions: RunLists, width, default=0.0, sum=
     return out
 
 
+def _window_door(rl, width, default=None, clip=(0, 0), capacity=None):
+    """wtamd_runs_bin (default given) or wtamd_runs_smooth (default None) over every segment of `rl`.  Returns (rc, runs
+    needed, (seg_off, start, finish, value) arrays); the arrays start out filled with -1 and a refused call leaves them so."""
+    import torch
+    dev = torch.device("cuda", torch.cuda.current_device())
+    n_seg = rl.n_chrom * rl.n_tracks
+    seg = np.ascontiguousarray(rl.seg_off, np.int64)
+    w = max(int(width), 1)
+    if capacity is None:
+        s64, f64 = np.asarray(rl.start, np.int64), np.asarray(rl.finish, np.int64)
+        if default is not None:
+            capacity = int(((f64 - 2) // w - (s64 - 1) // w + 1).sum()) if len(s64) else 0
+        else:
+            capacity = sum(int(f64[b - 1]) - max(1, int(s64[a]) - w // 2) + w for a, b in zip(seg[:-1], seg[1:]) if b > a)
+            if tuple(clip) != (0, 0):
+                capacity = min(capacity, max(int(clip[1]) - int(clip[0]), 0) * n_seg)
+    cap = max(int(capacity), 0)
+    s = torch.from_numpy(np.ascontiguousarray(rl.start, np.int32)).to(dev)
+    f = torch.from_numpy(np.ascontiguousarray(rl.finish, np.int32)).to(dev)
+    v = torch.from_numpy(np.ascontiguousarray(rl.value)).to(dev)
+    os_ = torch.full((max(cap, 1),), -1, dtype=torch.int32, device=dev)
+    of = torch.full((max(cap, 1),), -1, dtype=torch.int32, device=dev)
+    ov = torch.full((max(cap, 1),), -1.0, dtype=torch.float64, device=dev)
+    oseg = np.zeros(n_seg + 1, np.int64)
+    n_out = C.c_int64()
+    is64 = 1 if rl.value.dtype == np.float64 else 0
+    L = _lib.lib()
+    if default is not None:
+        rc = L.wtamd_runs_bin(n_seg, seg.ctypes.data, s.data_ptr(), f.data_ptr(), v.data_ptr(), is64, int(width), float(default), cap,
+                              os_.data_ptr(), of.data_ptr(), ov.data_ptr(), oseg.ctypes.data, C.byref(n_out), None)
+    else:
+        rc = L.wtamd_runs_smooth(n_seg, seg.ctypes.data, s.data_ptr(), f.data_ptr(), v.data_ptr(), is64, int(width), int(clip[0]), int(clip[1]), cap,
+                                 os_.data_ptr(), of.data_ptr(), ov.data_ptr(), oseg.ctypes.data, C.byref(n_out), None)
+    return rc, n_out.value, (oseg, os_.cpu().numpy(), of.cpu().numpy(), ov.cpu().numpy())
+
+
+def _window_runlists(rl, rc, m, out, defaults):
+    _lib.check(rc)
+    oseg, os_, of, ov = out
+    return RunLists(rl.n_chrom, rl.n_tracks, oseg, os_[:m], of[:m], ov[:m], defaults, rl.chrom_names)
+
+
+def bin_runlists(rl: RunLists, width):
+    """The reference's `bin` (BinningWiggleIterator, unaryOps.c:963-1036) over every track of `rl` on device (wtamd_runs_bin):
+    the grid bins [1 + k width, 1 + (k + 1) width) a run intersects, each with the sum of covered x value plus the track's
+    default over what is not covered; f64 values, defaults x width.  The runs must not overlap and start at 1 or above
+    (include/wiggletools_amd.h)."""
+    n_seg = rl.n_chrom * rl.n_tracks
+    if len(set(np.asarray(rl.defaults, np.float64).view(np.uint64).tolist())) > 1:
+        raise ValueError("bin: the tracks of one call share one default")
+    d = float(rl.defaults[0]) if n_seg and len(rl.defaults) else 0.0
+    rc, m, out = _window_door(rl, width, d)
+    return _window_runlists(rl, rc, m, out, np.asarray(rl.defaults, np.float64) * width)
+
+
+def smooth_runlists(rl: RunLists, width, clip=(0, 0)):
+    """The reference's `smooth` (SmoothWiggleIterator, unaryOps.c:1039-1162) over every track of `rl` on device
+    (wtamd_runs_smooth): one run per position with the mean of the window of `width` positions around it, by the reference's
+    rules at the ends of a chromosome; clip = (lo, hi) delivers the positions of [lo, hi) only.  The runs must not overlap and
+    start at 1 or above (include/wiggletools_amd.h)."""
+    rc, m, out = _window_door(rl, width, None, clip)
+    return _window_runlists(rl, rc, m, out, rl.defaults)
+
+
 class TrackSet:
     """N tracks resident in HBM (wtamd_trackset)."""
 
