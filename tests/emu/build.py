@@ -4,6 +4,8 @@ import os
 import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+# the kernels' bodies, which wt_emu.cpp executes (csrc/wt_exec.h)
+KERNEL_TEXTS = ("wt_exec.h", "wt_reduce_kernel.h", "wt_patch_kernel.h", "wt_delta_kernel.h", "wt_walk_kernel.h")
 
 
 def _compile(so, deps, cmd_tail):
@@ -26,7 +28,8 @@ def build(force=False):
             os.path.join(HERE, "..", "..", "wiggletools_amd", "csrc", "wt_plan.h"),
             os.path.join(HERE, "..", "..", "wiggletools_amd", "csrc", "wt_delta.h"),
             os.path.join(HERE, "..", "..", "wiggletools_amd", "csrc", "wt_walk.h"),
-            os.path.join(HERE, "..", "..", "wiggletools_amd", "csrc", "wt_mwalk.h")]
+            os.path.join(HERE, "..", "..", "wiggletools_amd", "csrc", "wt_mwalk.h")] + \
+        [os.path.join(HERE, "..", "..", "wiggletools_amd", "csrc", h) for h in KERNEL_TEXTS]
     if not force and os.path.exists(so) and all(os.path.getmtime(so) >= os.path.getmtime(s) for s in srcs):
         return so
     if force and os.path.exists(so):
@@ -39,7 +42,7 @@ def build_variant(name, flags):
     not the default, e.g. -DWT_DELTA_PARK=2), rebuilt when a source is newer."""
     so = os.path.join(HERE, "libwt_emu_%s.so" % name)
     csrc = os.path.join(HERE, "..", "..", "wiggletools_amd", "csrc")
-    srcs = [os.path.join(HERE, "wt_emu.cpp")] + [os.path.join(csrc, h) for h in ("wt_core.h", "wt_plan.h", "wt_delta.h", "wt_walk.h", "wt_mwalk.h")]
+    srcs = [os.path.join(HERE, "wt_emu.cpp")] + [os.path.join(csrc, h) for h in ("wt_core.h", "wt_plan.h", "wt_delta.h", "wt_walk.h", "wt_mwalk.h") + KERNEL_TEXTS]
     if os.path.exists(so) and all(os.path.getmtime(so) >= os.path.getmtime(s) for s in srcs):
         return so
     return _compile(so, srcs, list(flags) + [srcs[0], "-lm"])
@@ -64,7 +67,7 @@ def build_dropin(force=False):
     csrc = os.path.join(HERE, "..", "..", "wiggletools_amd", "csrc")
     srcs = [os.path.join(HERE, "wt_emu.cpp"), os.path.join(HERE, "wt_pipe_emu.cpp"),
             os.path.join(csrc, "wt_iter_abi.cpp"), os.path.join(csrc, "wt_defaults.cpp"), os.path.join(csrc, "wt_bigwig.cpp")]
-    deps = srcs + [os.path.join(csrc, h) for h in ("wt_core.h", "wt_plan.h", "wt_delta.h", "wt_walk.h", "wt_mwalk.h", "wt_abi_common.h", "wt_abi_feeder.h", "wt_abi_reduce.h", "wt_abi_readers.h", "wt_abi_runs.h", "wt_abi_cover.h", "wt_abi_region.h", "wt_abi_apply.h", "wt_abi_profile.h", "wt_abi_bwdev.h", "wt_abi_ops.h", "wt_abi_integrators.h", "wt_bufreader.h", "wt_inflate.h", "wt_bwdev_core.h",
+    deps = srcs + [os.path.join(csrc, h) for h in ("wt_core.h", "wt_plan.h", "wt_delta.h", "wt_walk.h", "wt_mwalk.h") + KERNEL_TEXTS + ("wt_abi_common.h", "wt_abi_feeder.h", "wt_abi_reduce.h", "wt_abi_readers.h", "wt_abi_runs.h", "wt_abi_cover.h", "wt_abi_region.h", "wt_abi_apply.h", "wt_abi_profile.h", "wt_abi_bwdev.h", "wt_abi_ops.h", "wt_abi_integrators.h", "wt_bufreader.h", "wt_inflate.h", "wt_bwdev_core.h",
                                                     "wt_mapop.h", "wt_bigwig_int.h")] + \
         [os.path.join(HERE, "..", "..", "include", "wiggletools_amd.h"), os.path.join(HERE, "wt_inflate_emu.h")]
     if not force and os.path.exists(so) and all(os.path.getmtime(so) >= os.path.getmtime(s) for s in deps):

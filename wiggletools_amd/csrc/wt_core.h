@@ -135,6 +135,16 @@ struct WtParams {
     int32_t delta_ns;             // difference-array launches: sets per position (0 / 1: one; 2: TTestReduction, wt_delta.h)
 };
 
+// Second argument of wt_patch_kernel (wt_patch_kernel.h): the windows the difference-array launch recorded
+struct WtPatchArgs {
+    const int32_t *bad_list;            // difference-array window ids (slot order)
+    const long long *bad_goff;          // first run of each
+    const unsigned long long *n_bad;    // how many (device counter of the difference-array launch)
+    const int32_t *d_win_chrom;         // the difference-array launch's window tables
+    const int64_t *d_c_first_win;
+    int ratio;                          // its window width / this launch's
+};
+
 // Block-shared scalars (live in LDS at off_shared)
 struct WtShared {
     long long ticket;

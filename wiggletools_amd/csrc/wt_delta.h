@@ -1483,6 +1483,41 @@ WT_DEV void wt_delta_scan3_val(const WtParams &P, WtCtx &c, WtDeltaCtx &d, const
     }
 }
 
+// the calls of the kernels' text (wt_delta_kernel.h) that the emulator runs as two fragments; GUARD: the call's `if (...)`, or nothing
+#define WT_DELTA_RANGES_W2(P, c, d, tid, nt, tile) wt_delta_ranges_w2(P, c, d, tid, nt, tile)
+#define WT_DELTA_SCAN_W1(GUARD, QQ, P, c, d, L, tid, nts) GUARD wt_delta_scan_w1<QQ>(P, c, d, L, tid, nts)
+#define WT_DELTA_SCAN_W1_TT(GUARD, P, c, d, L, tid, nts) GUARD wt_delta_scan_w1_tt(P, c, d, L, tid, nts)
+#define WT_DELTA_SCAN_W1_MM(P, c, d, wc, tid, nt) wt_delta_scan_w1_mm(P, c, d, wc, tid, nt)
+
+#else
+// ---------------------------------------------------------------------------
+// The emulator's place for the device flavours above (wt_exec.h; tests/emu/wt_emu.cpp lists them: NOT vouched for by the
+// wave-order tests): the LDS-only phases, one fragment each, WT_SUBSYNC where the device's wave scan needs no barrier.
+// ---------------------------------------------------------------------------
+WT_DEV void wt_delta_ranges_w1(const WtParams &P, WtCtx &c, WtDeltaCtx &d, int c0, int tid, int nt) { wt_delta_ranges1(P, c, d, c0, tid, nt); }
+#define WT_DELTA_RANGES_W2(P, c, d, tid, nt, tile) \
+    WT_DO() { wt_delta_ranges2(P, c, d, tid, nt); } WT_END WT_SUBSYNC; WT_DO() { wt_delta_ranges3(P, c, d, tid, nt, tile); } WT_END
+#define WT_DELTA_SCAN_W1(GUARD, QQ, P, c, d, L, tid, nts) \
+    WT_DO() { GUARD wt_delta_scan1<QQ>(P, c, d, L, tid, nts); } WT_END WT_SUBSYNC; WT_DO() { GUARD wt_delta_scan2<QQ>(P, c, d, tid, nts); } WT_END
+#define WT_DELTA_SCAN_W1_TT(GUARD, P, c, d, L, tid, nts) \
+    WT_DO() { GUARD wt_delta_scan1_tt(P, c, d, L, tid, nts); } WT_END WT_SUBSYNC; WT_DO() { GUARD wt_delta_scan2_tt(P, c, d, tid, nts); } WT_END
+// (wt_delta_scan2_mm leaves the whole prefix in LDS: nothing for the lane to carry to wt_delta_scan3_mm)
+#define WT_DELTA_SCAN_W1_MM(P, c, d, wc, tid, nt) \
+    WT_DO() { int32_t tc_; wt_delta_scan1_mm(P, c, d, tc_, tid, nt); wc = 0; } WT_END WT_SUBSYNC; WT_DO() { wt_delta_scan2_mm(P, c, d, tid, nt); } WT_END
+// wt_delta_escan_wave: a fragment runs the lanes of a wavefront one after the other, lane 0 first -- it does the LDS-only
+// scan of all 64 (wt_phase_escan)
+WT_DEV unsigned wt_delta_escan_wave(const WtParams &P, WtCtx &c, int lane) {
+    if (lane == 0)
+        for (int l = 0; l < 64; l++) wt_phase_escan(P, c, l, 64);
+    return (unsigned) c.epfx[P.n_words];
+}
+// Sum / Mean's early-publish route (EP, wt_delta_kernel.h) is wave code throughout: the emulator is built with
+// WT_DELTA_EARLY_PUBLISH 0 and follows the kernel's other branch.  What the discarded branch names, for two-phase lookup:
+uint32_t wt_waves_before32(const uint32_t *arr, int first, int wave, int lane);
+uint32_t wt_delta_scan3_cov(const WtParams &P, WtCtx &c, WtDeltaCtx &d, const WtDeltaLane &L, uint32_t &em_out, int tid, int nt);
+template <int OP> void wt_delta_scan3_val(const WtParams &P, WtCtx &c, WtDeltaCtx &d, const WtDeltaLane &L, WtLane<WT_DELTA_K> &out, int emin, int tid, int nt);
+template <int OP> void wt_delta_stage_ep(const WtParams &P, WtCtx &c, WtDeltaCtx &d, const WtLane<WT_DELTA_K> &L, unsigned em, unsigned um, unsigned idx, int tid, int nt);
+void wt_delta_note_offset_ep(const WtParams &P, WtCtx &c, int lane);
 #endif
 
 #endif  // WT_DELTA_H_

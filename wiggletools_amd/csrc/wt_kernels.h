@@ -1,7 +1,7 @@
 // wt_kernels.h -- what the engine (wt_engine.hip; the pipeline reaches the kernels through it, wt_trackset.h) needs of the
-// kernel units: the launch record, the patch kernel's arguments, the kernels' launch bounds and one launch entry per kernel family.  The kernels are templates in
-// wt_reduce_kernel.h / wt_delta_kernel.h, instantiated by op in wt_reduce_stream.hip, wt_reduce_moments.hip,
-// wt_reduce_order.hip, wt_patch_kernels.hip and wt_delta_kernels.hip; wt_walk.hip holds the walking kernels.
+// kernel units: the launch record (the patch kernel's arguments: WtPatchArgs, wt_core.h), the kernels' launch bounds and one launch entry per kernel family.  The kernels are templates in
+// wt_reduce_kernel.h / wt_patch_kernel.h / wt_delta_kernel.h / wt_walk_kernel.h (wt_exec.h), instantiated in wt_reduce_stream.hip,
+// wt_reduce_moments.hip, wt_reduce_order.hip, wt_patch_kernels.hip, wt_delta_kernels.hip and wt_walk.hip.
 #ifndef WT_KERNELS_H_
 #define WT_KERNELS_H_
 
@@ -18,15 +18,6 @@ struct WtLaunch {
     char **gscratch = nullptr;
     size_t *gscratch_bytes = nullptr;
     hipError_t err = hipSuccess;
-};
-
-struct WtPatchArgs {
-    const int32_t *bad_list;            // difference-array window ids (slot order)
-    const long long *bad_goff;          // first run of each
-    const unsigned long long *n_bad;    // how many (device counter of the difference-array launch)
-    const int32_t *d_win_chrom;         // the difference-array launch's window tables
-    const int64_t *d_c_first_win;
-    int ratio;                          // its window width / this launch's
 };
 
 // launch bounds of the kernels, as compiled into the units that own them

@@ -1,14 +1,18 @@
 // wt_reduce_kernel.h -- wt_reduce_kernel as a template (logic in wt_core.h): persistent workgroups, one alignment window per
 // ticket: bitmap multiplexer + per-run reducer + ordered output -- every reducer, any track count.  wt_reduce_stream.hip,
-// wt_reduce_moments.hip and wt_reduce_order.hip instantiate it for their ops.  WT_MAX_BLOCK, WT_MIN_WAVES and the WT_MARK / WT_TICK
-// macros (defined in the kernel's body) also serve wt_patch_kernel and wt_delta_kernel.  Compiled only by hipcc --offload-arch=gfx950.
+// wt_reduce_moments.hip and wt_reduce_order.hip instantiate it for their ops.  One text (wt_exec.h): hipcc compiles it for gfx950,
+// tests/emu/wt_emu.cpp runs the same body on the CPU; the launch functor below is the device's alone.  WT_MAX_BLOCK and
+// WT_MIN_WAVES also serve wt_patch_kernel.
 #ifndef WT_REDUCE_KERNEL_H_
 #define WT_REDUCE_KERNEL_H_
 
+#ifndef WT_EMU
 #include "../../include/wiggletools_amd.h"
 #include "wt_plan.h"
 #include "wt_kernels.h"
 #include "wt_launch.h"
+#endif
+#include "wt_exec.h"
 
 #define WT_MAX_BLOCK 512
 // minimum waves per SIMD the register allocator must leave room for (MI355X_MICROARCH:
@@ -24,32 +28,18 @@ template <int OP, class ValT, class ScrT, int K, bool MULTI, int NR>
 // (register columns, NR > 0: 256 lanes; the column + the exchange network's temporaries need more
 //  than the 168 VGPRs three waves per SIMD leave -- with that bound the compiler spilled 250
 //  registers into the middle of the network -- so NR = 128 runs two waves per SIMD, NR = 64 three)
-__global__ void __launch_bounds__(NR > 0 ? 256 : WT_MAX_BLOCK, NR > 0 ? (NR > 64 ? 2 : (NR > 32 ? 3 : 4)) : WT_MIN_WAVES(K)) wt_reduce_kernel(const WtParams P) {
-    extern __shared__ __attribute__((aligned(16))) char wt_lds[];
+WT_KERNEL(wt_reduce_kernel, (NR > 0 ? 256 : WT_MAX_BLOCK, NR > 0 ? (NR > 64 ? 2 : (NR > 32 ? 3 : 4)) : WT_MIN_WAVES(K)), const WtParams P) {
+    WT_LDS(wt_lds);
     WtCtx c;
     wt_ctx_init(c, P, wt_lds);
     // global slab of this workgroup: [value columns, if they do not fit LDS][MWU attributes]
     const size_t slab = (size_t) P.g_scratch_slab + (size_t) P.g_attr_slab;
     if (MULTI && (OP == WT_OP_MEDIAN || OP == WT_OP_MWU) && P.g_scratch_slab)
-        c.scratch = P.g_scratch + (size_t) blockIdx.x * slab;
-    if (OP == WT_OP_MWU) c.attr = P.g_scratch + (size_t) blockIdx.x * slab + (size_t) P.g_scratch_slab;
-    WtLane<K> L;
-    const int tid = threadIdx.x, nt = blockDim.x;
-#ifdef WT_MARK_ONLY
-#define WT_MARK(x) do { if ((x) == WT_MARK_ONLY && (tid & 63) == 0) { P.debug[2 + (tid >> 6)] = (unsigned long long) (x); __threadfence_system(); } } while (0)
-#elif defined(WT_DEBUG_MARK)
-#define WT_MARK(x) do { if ((tid & 63) == 0) { if (tid == 0) { P.debug[0] = (unsigned long long) (x); P.debug[1] = (unsigned long long) k_dbg; } P.debug[2 + (tid >> 6)] = (unsigned long long) (x); __threadfence_system(); } } while (0)
-#else
-#define WT_MARK(x) do { } while (0)
-#endif
-#ifdef WT_PROFILE
-#define WT_TICK(slot) do { if (tid == 0) { const unsigned long long t_ = __builtin_readcyclecounter(); \
-        prof[slot] += t_ - t_last; t_last = t_; } } while (0)
-    unsigned long long prof[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long t_last = __builtin_readcyclecounter();
-#else
-#define WT_TICK(slot) do { } while (0)
-#endif
+        c.scratch = P.g_scratch + (size_t) WT_WG * slab;
+    if (OP == WT_OP_MWU) c.attr = P.g_scratch + (size_t) WT_WG * slab + (size_t) P.g_scratch_slab;
+    WT_REG(L, WtLane<K>);
+    WT_THREAD_IDS;
+    WT_PROF_BEGIN;
     long long k_dbg = -1;
     (void) k_dbg;
     // Window tickets.  The lane-0 work at the end of one iteration (statistics) and at the start of
@@ -59,19 +49,19 @@ __global__ void __launch_bounds__(NR > 0 ? 256 : WT_MAX_BLOCK, NR > 0 ? (NR > 64
     // ticket: every wave re-reads the stale ticket and the workgroup never terminates (observed on
     // MI355X; any instruction between the two regions hides it).  So the next ticket is taken in the
     // same lane-0 block as the statistics, followed by the barrier that publishes it.
-    if (tid == 0) c.sh->ticket = (long long) wt_glb_add64(&P.counters[WT_CTR_TICKET], 1ull);
+    WT_DO() { if (tid == 0) c.sh->ticket = (long long) wt_glb_add64(&P.counters[WT_CTR_TICKET], 1ull); } WT_END
     if (NR > 0)
-        for (int i = tid; i < P.n_tracks; i += nt) c.dflt32[i] = (float) P.defaults[i];
-    __syncthreads();
+        WT_DO() { for (int i = tid; i < P.n_tracks; i += nt) c.dflt32[i] = (float) P.defaults[i]; } WT_END
+    WT_SYNC;
     for (;;) {
         WT_MARK(1);
         const long long k = c.sh->ticket;
         k_dbg = k;
         WT_MARK(2);
         if (k >= P.n_windows) break;
-        if (tid == 0) wt_phase_header(P, c, k);
-        wt_phase_zero(P, c, true, tid, nt);
-        __syncthreads();
+        WT_DO(k) { if (tid == 0) wt_phase_header(P, c, k); } WT_END
+        WT_DO() { wt_phase_zero(P, c, true, tid, nt); } WT_END
+        WT_SYNC;
         WT_TICK(0);
         // pass A: every track's breakpoints and coverage enter U / cover[]; with one chunk the
         // per-track bitmaps stay resident for the evaluation
@@ -82,46 +72,46 @@ __global__ void __launch_bounds__(NR > 0 ? 256 : WT_MAX_BLOCK, NR > 0 ? (NR > 64
         // tile, whose rows need the look-back offset first.
         constexpr bool FUSE = MULTI && OP != WT_OP_MULTIPLEX;
         constexpr int npass = wt_eval_passes(OP);
-        WtAcc<K, NR> A;
-        wt_eval_init<OP, K>(A);
+        WT_REG(A, WtAcc<K, NR>);
+        WT_DO() { wt_eval_init<OP, K>(WT_R(A)); } WT_END
         for (int ch = 0; ch < n_chunks; ch++) {
             const int t_lo = ch * NC, t_hi = (t_lo + NC < N) ? t_lo + NC : N;
             if (MULTI && ch > 0) {
-                wt_phase_zero(P, c, false, tid, nt);
-                __syncthreads();
+                WT_DO() { wt_phase_zero(P, c, false, tid, nt); } WT_END
+                WT_SYNC;
             }
             WT_MARK(3);
-            wt_phase_load<ValT>(P, c, t_lo, t_hi, true, tid, nt);
-            __syncthreads();
+            WT_DO(t_lo, t_hi) { wt_phase_load<ValT>(P, c, t_lo, t_hi, true, tid, nt); } WT_END
+            WT_SYNC;
             WT_TICK(1);
             WT_MARK(4);
-            wt_phase_count_a(P, c, t_lo, t_hi, tid, nt);
-            __syncthreads();
+            WT_DO(t_lo, t_hi) { wt_phase_count_a(P, c, t_lo, t_hi, tid, nt); } WT_END
+            WT_SYNC;
             WT_MARK(5);
-            wt_phase_count_b(P, c, t_lo, t_hi, tid, nt);
-            __syncthreads();
+            WT_DO(t_lo, t_hi) { wt_phase_count_b(P, c, t_lo, t_hi, tid, nt); } WT_END
+            WT_SYNC;
             WT_TICK(2);
             if (FUSE) {     // first evaluation pass rides on this sweep (every position: E is not known yet)
-                wt_phase_eval_chunk<OP, ValT, ScrT, K>(P, c, A, 0, t_lo, t_hi, true, tid, nt);
-                __syncthreads();
+                WT_DO(t_lo, t_hi) { wt_phase_eval_chunk<OP, ValT, ScrT, K>(P, c, WT_R(A), 0, t_lo, t_hi, true, tid, nt); } WT_END
+                WT_SYNC;
                 WT_TICK(4);
             }
         }
-        if (FUSE && npass == 2) wt_eval_mid<OP, K>(P, A);
+        if (FUSE && npass == 2) WT_DO() { wt_eval_mid<OP, K>(P, WT_R(A)); } WT_END
         WT_MARK(6);
-        wt_phase_emask(P, c, OP == WT_OP_TTEST || OP == WT_OP_MWU, tid, nt);
-        __syncthreads();
+        WT_DO() { wt_phase_emask(P, c, OP == WT_OP_TTEST || OP == WT_OP_MWU, tid, nt); } WT_END
+        WT_SYNC;
         WT_MARK(7);
-        wt_phase_escan(P, c, tid, nt);
-        __syncthreads();
+        WT_DO() { wt_phase_escan(P, c, tid, nt); } WT_END
+        WT_SYNC;
         WT_TICK(3);
         // the window's run count is known before the reducers run: publish it now, so that no
         // successor ever waits for our evaluation
         WT_MARK(8);
-        if (tid == 0) wt_lookback_publish(P, c, k);
+        WT_DO(k) { if (tid == 0) wt_lookback_publish(P, c, k); } WT_END
         if (OP == WT_OP_MULTIPLEX) {     // the tile rows are written by the evaluation: offset first
-            if (tid < 64) wt_lookback_complete(P, c, k, tid);
-            __syncthreads();
+            WT_DO(k) { if (tid < 64) wt_lookback_complete(P, c, k, tid); } WT_END
+            WT_SYNC;
         }
         WT_MARK(9);
 #pragma unroll
@@ -129,49 +119,50 @@ __global__ void __launch_bounds__(NR > 0 ? 256 : WT_MAX_BLOCK, NR > 0 ? (NR > 64
             for (int ch = 0; ch < n_chunks; ch++) {
                 const int t_lo = ch * NC, t_hi = (t_lo + NC < N) ? t_lo + NC : N;
                 if (MULTI) {
-                    wt_phase_zero(P, c, false, tid, nt);
-                    __syncthreads();
-                    wt_phase_load<ValT>(P, c, t_lo, t_hi, false, tid, nt);
-                    __syncthreads();
-                    wt_phase_count_a(P, c, t_lo, t_hi, tid, nt);
-                    __syncthreads();
-                    wt_phase_count_b(P, c, t_lo, t_hi, tid, nt);
-                    __syncthreads();
+                    WT_DO() { wt_phase_zero(P, c, false, tid, nt); } WT_END
+                    WT_SYNC;
+                    WT_DO(t_lo, t_hi) { wt_phase_load<ValT>(P, c, t_lo, t_hi, false, tid, nt); } WT_END
+                    WT_SYNC;
+                    WT_DO(t_lo, t_hi) { wt_phase_count_a(P, c, t_lo, t_hi, tid, nt); } WT_END
+                    WT_SYNC;
+                    WT_DO(t_lo, t_hi) { wt_phase_count_b(P, c, t_lo, t_hi, tid, nt); } WT_END
+                    WT_SYNC;
                 }
-                wt_phase_eval_chunk<OP, ValT, ScrT, K>(P, c, A, pass, t_lo, t_hi, false, tid, nt);
-                if (MULTI) __syncthreads();     // the next chunk overwrites the bitmaps
+                WT_DO(pass, t_lo, t_hi) { wt_phase_eval_chunk<OP, ValT, ScrT, K>(P, c, WT_R(A), pass, t_lo, t_hi, false, tid, nt); } WT_END
+                if (MULTI) WT_SYNC;     // the next chunk overwrites the bitmaps
             }
-            if (pass == 0 && npass == 2) wt_eval_mid<OP, K>(P, A);
+            if (pass == 0 && npass == 2) WT_DO() { wt_eval_mid<OP, K>(P, WT_R(A)); } WT_END
         }
-        wt_phase_eval_finish<OP, ValT, ScrT, K>(P, c, A, L, tid, nt);
+        WT_DO() { wt_phase_eval_finish<OP, ValT, ScrT, K>(P, c, WT_R(A), WT_R(L), tid, nt); } WT_END
         if (OP == WT_OP_MWU && NR == 0) {      // the value columns are complete: rank with every lane, then the tie scan
-            __syncthreads();
-            wt_phase_mwu_rank<ScrT>(P, c, tid, nt);
-            __syncthreads();
-            wt_phase_mwu_tail<K>(P, c, A, L, tid, nt);
+            WT_SYNC;
+            WT_DO() { wt_phase_mwu_rank<ScrT>(P, c, tid, nt); } WT_END
+            WT_SYNC;
+            WT_DO() { wt_phase_mwu_tail<K>(P, c, WT_R(A), WT_R(L), tid, nt); } WT_END
         }
         WT_TICK(4);
         WT_MARK(10);
-        if (OP != WT_OP_MULTIPLEX && tid < 64) wt_lookback_complete(P, c, k, tid);
-        __syncthreads();
+        WT_DO(k) { if (OP != WT_OP_MULTIPLEX && tid < 64) wt_lookback_complete(P, c, k, tid); } WT_END
+        WT_SYNC;
         WT_TICK(5);
         WT_MARK(11);
-        wt_phase_write<OP, ValT, K>(P, c, L, tid, nt);
-        __syncthreads();
+        WT_DO() { wt_phase_write<OP, ValT, K>(P, c, WT_R(L), tid, nt); } WT_END
+        WT_SYNC;
         WT_MARK(12);
-        if (tid == 0) {
-            wt_window_stats(P, c);
-            c.sh->ticket = (long long) wt_glb_add64(&P.counters[WT_CTR_TICKET], 1ull);
-        }
-        __syncthreads();
+        WT_DO() {
+            if (tid == 0) {
+                wt_window_stats(P, c);
+                c.sh->ticket = (long long) wt_glb_add64(&P.counters[WT_CTR_TICKET], 1ull);
+            }
+        } WT_END
+        WT_SYNC;
         WT_TICK(6);
     }
-#ifdef WT_PROFILE
-    if (tid == 0)
-        for (int q = 0; q < 8; q++) wt_glb_add64(&P.counters[WT_CTR_PROF + q], prof[q]);
-#endif
+    WT_PROF_END;
+    WT_KERNEL_END;
 }
 
+#ifndef WT_EMU
 // Launch functor of the general kernel for wt_dispatch_ops (wt_plan.h)
 struct WtReduceRun {
     WtLaunch &L;
@@ -195,5 +186,7 @@ struct WtReduceRun {
         L.err = hipGetLastError();
     }
 };
+
+#endif  // WT_EMU
 
 #endif  // WT_REDUCE_KERNEL_H_

@@ -183,6 +183,8 @@ WT_DEV void wt_walk_ranges3(WtDeltaCtx &d, int tid, int nt) {
     for (uint32_t b = (pfx + WT_DELTA_TILE - 1) / WT_DELTA_TILE; b * WT_DELTA_TILE < pfx + n && b < WT_WALK_TF; b++)
         d.tfirst[b] = (uint16_t) tid;
 }
+// (the emulator's place for wt_walk_ranges_w2, wt_exec.h)
+WT_DEV void wt_walk_ranges_w2(WtDeltaCtx &d, int tid, int nt) { wt_walk_ranges3(d, tid, nt); }
 #else
 WT_DEV void wt_walk_ranges_w2(WtDeltaCtx &d, int tid, int nt) {
     const int wave = tid >> 6;
