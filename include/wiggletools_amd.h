@@ -594,6 +594,52 @@ int wtamd_runs_smooth_host(int64_t n, const int32_t *start, const int32_t *finis
                            int32_t clip_lo, int32_t clip_hi,
                            int64_t capacity, int32_t *o_start, int32_t *o_finish, double *o_value, int64_t *n_out);
 
+/* Value histograms on device (csrc/wt_hist.hip): the reference's histogram() (src/plots.c:77-223; the parser's `histogram`)
+ * over whole run lists.  The layout of wtamd_runs_map: n_seg segments, seg_off a HOST array of n_seg + 1 offsets, start / finish
+ * / value (f32 or f64) DEVICE arrays; seg_row a HOST array of n_seg entries, the histogram row (0 .. n_rows - 1) of every
+ * segment, so chromosome-major and track-major lists both work; hist a DEVICE matrix of n_rows x width doubles, range2 two
+ * doubles on the HOST.  The runs need be neither sorted nor disjoint (the reference histograms raw iterators and counts
+ * overlapping intervals once each); the only rule per run is start < finish; fewer than 2^31 runs.
+ * THE RULE.  lo and hi are the minimum and maximum of all non-NaN values of all rows.  A run with a NaN value is skipped.  A
+ * run of value v and length L = finish - start adds L to column c of its row: c = 0 when lo == hi, otherwise
+ * c = (int) ((v - lo) * width / (hi - lo)) computed in double in exactly that order -- subtract, multiply by (double) width, one
+ * IEEE division --, and c == width becomes width - 1 (any quotient not below width lands there).  f32 values are widened
+ * first, so the same values in either width give the same bits.  The counters are unsigned 64-bit integers in LDS and in global
+ * memory, converted to double at the end (exact below 2^53): the result does not depend on the order of addition and is
+ * bit-reproducible.  A zero extreme comes back as +0.0.  When no non-NaN value exists, range2 comes back NaN, NaN and hist all
+ * zeros.
+ * flags.  WTAMD_HIST_RANGE_GIVEN: range2 is INPUT (lo, hi) and is not written; the range pass still validates.
+ * WTAMD_HIST_ACCUMULATE (needs RANGE_GIVEN): hist holds whole numbers below 2^53 from an earlier call over the same range; they
+ * are read back into the integer counters and added to.  So batches, and chromosomes on different GPUs, compose exactly:
+ * compute a range per part, take the min / max on the host, run every part with the range given, add the parts -- counts are
+ * integers, so any split gives the bits of the single call.
+ * WTAMD_ERR_ARG, NOTHING written to hist or range2: width < 1 or n_rows < 1 (or n_rows x width above 2^40); a seg_row outside
+ * [0, n_rows); a run with start >= finish; an infinite value (the reference's cast is undefined there); an unknown flag bit;
+ * ACCUMULATE without RANGE_GIVEN; with RANGE_GIVEN a NaN, infinite or inverted range or a non-NaN value outside it; with
+ * ACCUMULATE a cell of hist that is not a whole number in [0, 2^53).
+ * Departures from the reference, which streams with a provisional range and re-bins whenever a value leaves it:
+ *  1. Its re-binning smears mass by linear interpolation (raiseMaxNRows, plots.c:137-146); here bins are exact over the final
+ *     range.  Lengths 4, values 0, 1, 0.5, 2, 0.25, width 4: the reference gives 8 8 0 4, the exact answer, given here, is 8 4 4 4.
+ *  2. Its lowering re-bin reads and writes one column past each row (lowerMinNRows, plots.c:108) and has no defined result.
+ *  3. At width 1 it loses all earlier mass when the second distinct value is lower (plots.c:113-116); here width 1 gives the
+ *     total span.
+ *  4. It keeps the sign of the run that set a zero extreme; here a zero extreme is +0.0 (seen only in the printed centre of an
+ *     all -0.0 input).
+ * The two are equal, bit for bit, exactly when no value lies outside the interval spanned by the stream's first two distinct
+ * non-NaN values and either width >= 2 or the second of them is higher (the stream runs row 0 first, in order).
+ * Synchronous on `stream`; temporary memory from the device pool: 8 bytes per cell of hist, 16 bytes per 16384 runs (per stretch
+ * of consecutive segments of one row), 32 bytes of scalars. */
+#define WTAMD_HIST_RANGE_GIVEN 1u   /* range2 is INPUT: lo, hi */
+#define WTAMD_HIST_ACCUMULATE  2u   /* hist already holds a histogram over the same range: add to it */
+int wtamd_runs_histogram(int64_t n_seg, const int64_t *seg_off, const int32_t *seg_row, int32_t n_rows,
+                         const int32_t *start, const int32_t *finish, const void *value, int value_is_f64,
+                         int32_t width, uint32_t flags, double *range2, double *hist, void *stream);
+/* The same over run lists and a matrix held in HOST arrays (what wtamd_histogram calls): device memory, copies and the call on
+ * the null stream. */
+int wtamd_runs_histogram_host(int64_t n_seg, const int64_t *seg_off, const int32_t *seg_row, int32_t n_rows,
+                              const int32_t *start, const int32_t *finish, const double *value,
+                              int32_t width, uint32_t flags, double *range2, double *hist);
+
 /* Run compression on device (reference CompressionWiggleIterator, unaryOps.c:235-253, which the
  * default writer applies, wigWriter.c:263-267): adjacent runs of one chromosome merge while
  * start == previous finish and (both NaN or |value - value of the group's first run| < 1e-6).
@@ -856,6 +902,23 @@ Multiplexer *wtamd_ProfileMultiplexer(WiggleIterator *regions, int width, Wiggle
  * reference's smooth, whose running sum carries over from one chromosome to the next, every chromosome starts from 0. */
 WiggleIterator *wtamd_BinIterator(WiggleIterator *child, int width);
 WiggleIterator *wtamd_SmoothIterator(WiggleIterator *child, int width);
+/* The reference's histogram(), normalize_histogram() and print_histogram() (plots.c:167-223; `histogram`, commandParser.c
+ * readHistogram) on wtamd_runs_histogram: row r is wigs[r].  Every child is drained whole (in blocks where it is a bulk source,
+ * pop by pop otherwise) and its runs are held, 16 bytes per run of host memory, until the range is known; then one call of
+ * wtamd_runs_histogram_host.  WTAMD_NO_DEVICE_HIST=1 (or a build of the drop-in layer without the HIP units) computes the same
+ * bits with a host sweep.  normalize: the row sum over the columns in order, then the divisions; an empty row gives NaN.
+ * print: "%f" of position + step / 2, "\t%f" per row, position += step iteratively, as the reference does.  width < 1,
+ * count < 1, a run with start >= finish or an infinite value: a message and exit(1).  A first row without a non-NaN value, on
+ * which the reference does not return, gives a NaN range and zeros.  The departures listed at wtamd_runs_histogram hold. */
+typedef struct wtamd_histogram_st wtamd_Histogram;
+wtamd_Histogram *wtamd_histogram(WiggleIterator **wigs, int count, int width);
+void wtamd_normalize_histogram(wtamd_Histogram *hist);
+void wtamd_print_histogram(wtamd_Histogram *hist, FILE *file);
+int wtamd_histogram_width(const wtamd_Histogram *hist);
+int wtamd_histogram_count(const wtamd_Histogram *hist);
+const double *wtamd_histogram_row(const wtamd_Histogram *hist, int row);
+void wtamd_histogram_range(const wtamd_Histogram *hist, double *lo_hi2);
+void wtamd_destroy_histogram(wtamd_Histogram *hist);
 /* BigWig reader: the role of the reference's BigWiggleReader (src/bigWiggleReader.c:147-151) on this
  * library's own section decoder -- chromosomes in strcmp order, 1-based starts, box != 0: intervals
  * cut at the reference reader's 10 000-bp stretch edges (what `write_bg` parity needs); one producer

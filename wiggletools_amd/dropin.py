@@ -151,6 +151,61 @@ def smooth_iterator(child, width):
     return L.wtamd_SmoothIterator(child, int(width))
 
 
+def _read_back(L, write):
+    """What write(FILE *) prints, through a temporary file of the C library."""
+    libc = C.CDLL(None)
+    libc.tmpfile.restype = C.c_void_p
+    libc.fclose.argtypes = libc.rewind.argtypes = libc.fflush.argtypes = [C.c_void_p]
+    libc.fread.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
+    libc.fread.restype = C.c_size_t
+    fp = libc.tmpfile()
+    if not fp:
+        raise OSError("tmpfile()")
+    try:
+        write(fp)
+        libc.fflush(fp)
+        libc.rewind(fp)
+        out, buf = [], C.create_string_buffer(1 << 16)
+        while True:
+            n = libc.fread(buf, 1, len(buf), fp)
+            if n == 0:
+                return b"".join(out).decode()
+            out.append(buf.raw[:n])
+    finally:
+        libc.fclose(fp)
+
+
+def histogram(iterators, width, normalize=False):
+    """wtamd_histogram: the reference's `histogram` of the iterators, one row each, over `width` value bins.  Returns
+    ((lo, hi), (rows, width) matrix, the text wtamd_print_histogram writes); normalize=True: after wtamd_normalize_histogram."""
+    L = _bind()
+    L.wtamd_histogram.restype = C.c_void_p
+    L.wtamd_histogram.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int]
+    L.wtamd_histogram_row.restype = C.POINTER(C.c_double)
+    L.wtamd_histogram_row.argtypes = [C.c_void_p, C.c_int]
+    for name in ("wtamd_normalize_histogram", "wtamd_destroy_histogram"):
+        getattr(L, name).restype = None
+        getattr(L, name).argtypes = [C.c_void_p]
+    L.wtamd_print_histogram.restype = None
+    L.wtamd_print_histogram.argtypes = [C.c_void_p, C.c_void_p]
+    L.wtamd_histogram_range.restype = None
+    L.wtamd_histogram_range.argtypes = [C.c_void_p, C.c_void_p]
+    L.wtamd_histogram_width.argtypes = L.wtamd_histogram_count.argtypes = [C.c_void_p]
+    arr = (C.c_void_p * len(iterators))(*iterators)
+    h = L.wtamd_histogram(arr, len(iterators), int(width))
+    try:
+        if normalize:
+            L.wtamd_normalize_histogram(h)
+        r2 = np.zeros(2, np.float64)
+        L.wtamd_histogram_range(h, r2.ctypes.data)
+        w, n = L.wtamd_histogram_width(h), L.wtamd_histogram_count(h)
+        m = np.array([np.ctypeslib.as_array(L.wtamd_histogram_row(h, r), shape=(w,)).copy() for r in range(n)])
+        text = _read_back(L, lambda fp: L.wtamd_print_histogram(h, fp))
+    finally:
+        L.wtamd_destroy_histogram(h)
+    return (float(r2[0]), float(r2[1])), m, text
+
+
 def bigwig_reader(path, box=True):
     """wtamd_BigWiggleReader: the reference's BigWiggleReader role (bigWiggleReader.c:147-151), bulk-capable."""
     return _bind().wtamd_BigWiggleReader(path.encode(), int(box))

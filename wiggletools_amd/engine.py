@@ -298,6 +298,43 @@ def smooth_runlists(rl: RunLists, width, clip=(0, 0)):
     return _window_runlists(rl, rc, m, out, rl.defaults)
 
 
+HIST_RANGE_GIVEN, HIST_ACCUMULATE = 1, 2      # WTAMD_HIST_*
+
+
+def _hist_door(rl, width, flags=0, range=None, hist=None, seg_row=None, n_rows=None):
+    """wtamd_runs_histogram over every segment of `rl`; row of a segment: its track, or seg_row[segment] with n_rows rows.
+    Returns (rc, range (2,), matrix (n_rows, width)).  Both outputs start out filled with -1 -- or hold `range` and `hist`, the
+    inputs of WTAMD_HIST_RANGE_GIVEN and WTAMD_HIST_ACCUMULATE -- and a refused call leaves them so."""
+    import torch
+    dev = torch.device("cuda", torch.cuda.current_device())
+    n_seg = rl.n_chrom * rl.n_tracks
+    seg = np.ascontiguousarray(rl.seg_off, np.int64)
+    rows = np.ascontiguousarray(np.tile(np.arange(rl.n_tracks), rl.n_chrom) if seg_row is None else seg_row, np.int32)
+    assert len(rows) == n_seg
+    nr = rl.n_tracks if n_rows is None else int(n_rows)
+    s = torch.from_numpy(np.ascontiguousarray(rl.start, np.int32)).to(dev)
+    f = torch.from_numpy(np.ascontiguousarray(rl.finish, np.int32)).to(dev)
+    v = torch.from_numpy(np.ascontiguousarray(rl.value)).to(dev)
+    shape = (max(nr, 1), max(int(width), 1))
+    if hist is None:
+        out = torch.full(shape, -1.0, dtype=torch.float64, device=dev)
+    else:
+        out = torch.from_numpy(np.ascontiguousarray(hist, np.float64).reshape(shape)).to(dev)
+    r2 = np.full(2, -1.0) if range is None else np.array(range, np.float64)
+    rc = _lib.lib().wtamd_runs_histogram(n_seg, seg.ctypes.data, rows.ctypes.data, nr, s.data_ptr(), f.data_ptr(), v.data_ptr(),
+                                         1 if rl.value.dtype == np.float64 else 0, int(width), int(flags), r2.ctypes.data, out.data_ptr(), None)
+    return rc, r2, out.cpu().numpy()
+
+
+def histogram_runlists(rl: RunLists, width):
+    """The reference's `histogram` (histogram(), src/plots.c:167-194) over `rl` on device (wtamd_runs_histogram), one row per
+    track: ((lo, hi), (n_tracks, width) matrix of base pairs per value bin).  Bins are exact over the final range
+    (include/wiggletools_amd.h lists where the reference, which re-bins as it streams, differs)."""
+    rc, r2, out = _hist_door(rl, width)
+    _lib.check(rc)
+    return (float(r2[0]), float(r2[1])), out
+
+
 class TrackSet:
     """N tracks resident in HBM (wtamd_trackset)."""
 
