@@ -640,6 +640,46 @@ int wtamd_runs_histogram_host(int64_t n_seg, const int64_t *seg_off, const int32
                               const int32_t *start, const int32_t *finish, const double *value,
                               int32_t width, uint32_t flags, double *range2, double *hist);
 
+/* Energy spectra on device (csrc/wt_energy.hip): the reference's EnergyIntegrator (src/statistics.c:345-391; the parser's
+ * `energy (wavelength) (iterator)`) over whole run lists, for any number of wavelengths from ONE read of the list.  The layout
+ * of wtamd_runs_histogram: n_seg segments, seg_off a HOST array of n_seg + 1 offsets, start / finish / value (f32 or f64) DEVICE
+ * arrays; wavelength a HOST array of n_wavelengths entries; reim a HOST array of 2 n_wavelengths doubles (real0, im0, real1,
+ * ...); the energy of a wavelength is real^2 + im^2 (wtamd_energy_finish).  seg_base: a HOST array of n_seg int64 offsets
+ * added to a segment's coordinates, or NULL for the reference's rule from 0 -- a segment's base is the sum of the last
+ * finishes of the non-empty segments before it; an empty segment adds nothing (its seg_base entry is not looked at).  end_base
+ * (HOST, may be NULL): the base a following segment would get -- the base of the last non-empty segment plus its last finish;
+ * without one, the last entry of seg_base, or 0 --, so batches, chromosomes served one at a time and shards on other GPUs
+ * chain: partial sums add, and a split agrees with the single call to rounding, not bit for bit.
+ * THE RULE.  Every position p = base + start .. base + finish - 1 of a run of value v adds v cos(-2 pi p / lam) to real and
+ * v sin(-2 pi p / lam) to im; gaps add nothing.  A run's sum is taken in closed form: with a = base + start (int64),
+ * L = finish - start, m = (2 a + L - 1) mod 2 lam (floor modulus) and q = L mod 2 lam, both exact integers,
+ * D = sinpi(q / lam) / sin(pi / lam): real += v D cospi(m / lam), im -= v D sinpi(m / lam); for lam == 1, real += v L.  f32 values
+ * are widened first, so the same values in either width give the same bits.  Against the exact value of the rule, real and
+ * im each lie within 2^-53 (48 + n) S, n the runs of the call and S = sum |v| L (DESIGN.md counts it).
+ * FIXED ORDER.  A lane adds its runs in index order, a workgroup merges its lanes in a fixed tree, a final pass merges the
+ * workgroups' partials in a fixed order; no floating-point atomics: the same list gives the same bits on every call.
+ * WTAMD_ERR_ARG, NOTHING written to reim or end_base: n_wavelengths < 1 or above 1024 (WEN_MAX_WAVELENGTHS); a wavelength
+ * < 1; a run with start >= finish; a segment that is not sorted and disjoint (start[i] < finish[i - 1]: put wtamd_runs_union in
+ * front, as the reference does); a segment with runs whose |base| exceeds 2^62 - 2^31 (base + coordinate outside +-2^62).
+ * DEPARTURES from the reference.  1. Positions are exact: no position goes through a double or an int product, so the result
+ * is defined beyond position 2^30 (where the reference's `-position * 2` overflows) and offsets are 64-bit (its int
+ * chrom_offset overflows on a human genome).  2. The values are correctly reduced closed forms, not running sums of libm calls
+ * on large arguments: agreement with the reference is to its own error bound, 2^-53 S (16 P / lam + B + 8) for largest
+ * position P and B base pairs, not bit for bit.  3. A NaN OR INFINITE value makes every real and im NaN (the reference can
+ * return +-inf for an infinity).
+ * Synchronous on `stream`; temporary memory from the device pool: 16 n_wavelengths bytes per 16384 runs, 48 n_wavelengths + 16
+ * bytes of table, outputs and scalars, 20 bytes per segment. */
+int wtamd_runs_energy(int64_t n_seg, const int64_t *seg_off, const int64_t *seg_base,
+                      const int32_t *start, const int32_t *finish, const void *value, int value_is_f64,
+                      int32_t n_wavelengths, const int32_t *wavelength, double *reim, int64_t *end_base, void *stream);
+/* The same over run lists held in HOST arrays (what wtamd_EnergyIntegrator calls): device memory, copies and the call on the
+ * null stream. */
+int wtamd_runs_energy_host(int64_t n_seg, const int64_t *seg_off, const int64_t *seg_base,
+                           const int32_t *start, const int32_t *finish, const double *value,
+                           int32_t n_wavelengths, const int32_t *wavelength, double *reim, int64_t *end_base);
+/* real^2 + im^2 of one wavelength's pair (statistics.c:365). */
+double wtamd_energy_finish(const double *reim2);
+
 /* Run compression on device (reference CompressionWiggleIterator, unaryOps.c:235-253, which the
  * default writer applies, wigWriter.c:263-267): adjacent runs of one chromosome merge while
  * start == previous finish and (both NaN or |value - value of the group's first run| < 1e-6).
@@ -919,6 +959,22 @@ int wtamd_histogram_count(const wtamd_Histogram *hist);
 const double *wtamd_histogram_row(const wtamd_Histogram *hist, int row);
 void wtamd_histogram_range(const wtamd_Histogram *hist, double *lo_hi2);
 void wtamd_destroy_histogram(wtamd_Histogram *hist);
+/* The reference's EnergyIntegrator (statistics.c:345-391; called where the parser calls it, commandParser.c:677-681) on
+ * wtamd_runs_energy, with the contract of the library's other integrators: pop it to the end, *(double *) data is then the
+ * result real^2 + im^2 (NaN before the end, statistics.c:389), `append` is the source, the default is the child's; behind the
+ * leading res, `data` keeps real and im where the reference's EnergyData has them.  The child is drained a chromosome at a time
+ * (in blocks where it is a bulk source, pop by pop otherwise; an overlapping child goes through the reference's union rule
+ * first), one wtamd_runs_energy_host call per chromosome with the running offset -- which grows by the last finish served when
+ * the chromosome changes, the priming pop adding 0 --, and the chromosomes' sums are added in genome order.  One pop serves one
+ * chromosome.  A seek carries the sums and the offset on, as the reference's does.  WTAMD_NO_DEVICE_ENERGY=1 (or a build of
+ * the drop-in layer without the HIP units) sweeps on the host by the same rule (equal to rounding).  A wavelength < 1, which
+ * the door refuses, is served by the reference's own per-position expression on the host: 0 gives NaN, a negative one what
+ * the reference gives.  A child that is not sorted or holds a run with start >= finish: a message and exit(1).  The
+ * departures listed at wtamd_runs_energy hold. */
+WiggleIterator *wtamd_EnergyIntegrator(WiggleIterator *child, int wavelength);
+/* n wavelengths from ONE drain of the child: reim[2 k], reim[2 k + 1] are what n integrators would hold as real and im, bit
+ * for bit.  WTAMD_OK, or WTAMD_ERR_ARG for n < 1 or n above 1024. */
+int wtamd_EnergySpectrum(WiggleIterator *child, int n, const int *wavelengths, double *reim);
 /* BigWig reader: the role of the reference's BigWiggleReader (src/bigWiggleReader.c:147-151) on this
  * library's own section decoder -- chromosomes in strcmp order, 1-based starts, box != 0: intervals
  * cut at the reference reader's 10 000-bp stretch edges (what `write_bg` parity needs); one producer

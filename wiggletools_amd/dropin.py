@@ -206,6 +206,33 @@ def histogram(iterators, width, normalize=False):
     return (float(r2[0]), float(r2[1])), m, text
 
 
+def energy_integrator(child, wavelength):
+    """wtamd_EnergyIntegrator: the reference's `energy (wavelength)` of `child`; pop it to the end (drain_pops), then
+    energy_result() reads (res, real, im) where the reference keeps them."""
+    L = _bind()
+    L.wtamd_EnergyIntegrator.restype = C.c_void_p
+    L.wtamd_EnergyIntegrator.argtypes = [C.c_void_p, C.c_int]
+    return L.wtamd_EnergyIntegrator(child, int(wavelength))
+
+
+def energy_result(wi):
+    """(res, real, im) of an energy integrator: the head of its `data` (res is NaN until it has been popped to the end)."""
+    data = C.cast(wi + 40, C.POINTER(C.c_void_p))[0]       # offsetof(struct wiggleIterator_st, data)
+    d = np.ctypeslib.as_array(C.cast(data, C.POINTER(C.c_double)), shape=(3,))
+    return float(d[0]), float(d[1]), float(d[2])
+
+
+def energy_spectrum(child, wavelengths):
+    """wtamd_EnergySpectrum: every wavelength from one drain of `child`.  Returns (reim (n, 2), energies (n,))."""
+    L = _bind()
+    L.wtamd_EnergySpectrum.restype = C.c_int
+    L.wtamd_EnergySpectrum.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    lam = np.ascontiguousarray(wavelengths, np.int32)
+    out = np.zeros((len(lam), 2), np.float64)
+    _lib.check(L.wtamd_EnergySpectrum(child, len(lam), lam.ctypes.data, out.ctypes.data))
+    return out, out[:, 0] * out[:, 0] + out[:, 1] * out[:, 1]
+
+
 def bigwig_reader(path, box=True):
     """wtamd_BigWiggleReader: the reference's BigWiggleReader role (bigWiggleReader.c:147-151), bulk-capable."""
     return _bind().wtamd_BigWiggleReader(path.encode(), int(box))

@@ -335,6 +335,43 @@ def histogram_runlists(rl: RunLists, width):
     return (float(r2[0]), float(r2[1])), out
 
 
+def _energy_door(rl, wavelengths, seg_base=None):
+    """wtamd_runs_energy over every segment of `rl`, in order, as ONE sequence (a track set of one track: its chromosomes).
+    Returns (rc, reim (n_wavelengths, 2), end_base).  The outputs start out filled with -1 and a refused call leaves them so."""
+    import torch
+    dev = torch.device("cuda", torch.cuda.current_device())
+    n_seg = rl.n_chrom * rl.n_tracks
+    seg = np.ascontiguousarray(rl.seg_off, np.int64)
+    lam = np.ascontiguousarray(wavelengths, np.int32)
+    sb = None if seg_base is None else np.ascontiguousarray(seg_base, np.int64)
+    assert sb is None or len(sb) == n_seg
+    s = torch.from_numpy(np.ascontiguousarray(rl.start, np.int32)).to(dev)
+    f = torch.from_numpy(np.ascontiguousarray(rl.finish, np.int32)).to(dev)
+    v = torch.from_numpy(np.ascontiguousarray(rl.value)).to(dev)
+    out = np.full((max(len(lam), 1), 2), -1.0)
+    end = np.full(1, -1, np.int64)
+    rc = _lib.lib().wtamd_runs_energy(n_seg, seg.ctypes.data, None if sb is None else sb.ctypes.data, s.data_ptr(), f.data_ptr(), v.data_ptr(),
+                                      1 if rl.value.dtype == np.float64 else 0, len(lam), lam.ctypes.data, out.ctypes.data, end.ctypes.data, None)
+    return rc, out, int(end[0])
+
+
+def energy_runlists(rl: RunLists, wavelengths):
+    """The reference's `energy` (EnergyIntegrator, src/statistics.c:345-391) of every track of `rl` on device (wtamd_runs_energy),
+    all wavelengths from one read of a track's runs: an (n_tracks, n_wavelengths) array of real^2 + im^2.  A chromosome is shifted
+    by the last finishes of the track's chromosomes before it, as the reference's offset rule has it; the runs of a chromosome
+    must be sorted and disjoint (include/wiggletools_amd.h lists where the reference, which sums position by position, differs)."""
+    out = np.zeros((rl.n_tracks, len(wavelengths)))
+    for t in range(rl.n_tracks):
+        segs = [(int(rl.seg_off[c * rl.n_tracks + t]), int(rl.seg_off[c * rl.n_tracks + t + 1])) for c in range(rl.n_chrom)]
+        idx = np.concatenate([np.arange(a, b) for a, b in segs] + [np.zeros(0, np.int64)]).astype(np.int64)
+        one = RunLists(rl.n_chrom, 1, np.concatenate([[0], np.cumsum([b - a for a, b in segs])]), rl.start[idx], rl.finish[idx], rl.value[idx],
+                       [rl.defaults[t]])
+        rc, reim, _ = _energy_door(one, wavelengths)
+        _lib.check(rc)
+        out[t] = reim[:, 0] * reim[:, 0] + reim[:, 1] * reim[:, 1]
+    return out
+
+
 class TrackSet:
     """N tracks resident in HBM (wtamd_trackset)."""
 
