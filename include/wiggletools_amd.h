@@ -680,6 +680,54 @@ int wtamd_runs_energy_host(int64_t n_seg, const int64_t *seg_off, const int64_t 
 /* real^2 + im^2 of one wavelength's pair (statistics.c:365). */
 double wtamd_energy_finish(const double *reim2);
 
+/* Wig and bedGraph text on device (csrc/wt_text.hip): the reference's writer, printBlock of TeeWiggleIterator
+ * (src/wigWriter.c:55-119; the parser's `write` and `write_bg`), over whole run lists: from a run list to the bytes of the
+ * file, byte for byte what the reference prints.  The layout of wtamd_runs_histogram: n_seg segments, seg_off a HOST array of
+ * n_seg + 1 offsets, start / finish / value (f32 or f64) DEVICE arrays; seg_name a HOST array of n_seg C strings of 1 to 255
+ * bytes, copied verbatim; text DEVICE memory of `capacity` bytes at any alignment.  The door prints the list it is given: it
+ * does not compress, sort or merge (wtamd_runs_compress is the writer's compression).
+ * THE RULE.  The writer numbers the runs it receives from 0, across chromosomes, and prints them in blocks of
+ * WTAMD_TEXT_BLOCK = 10000 consecutive entries (BLOCK_LENGTH).  Every block starts with pointByPoint = false, lastChrom = NULL,
+ * lastFinish = -1: nothing about the mode crosses a block boundary.  L = finish - start.  With WTAMD_TEXT_BEDGRAPH no entry
+ * is point-by-point; otherwise an entry is point-by-point iff the latest entry at or before it in its block with L < 2 or L > 5
+ * exists and has L < 2 (wigWriter.c:69-74 as a "last setter" scan: entries with 2 <= L <= 5 hold the mode).  A point-by-point
+ * entry prints L lines "%lf\n"; before them "fixedStep chrom=%s start=%i step=1\n" (start itself, 1-based) iff it is the
+ * first entry of its block, or the previous entry of the block is not point-by-point, or lies in another segment, or
+ * start > the previous entry's finish.  Any other entry prints "%s\t%i\t%i\t%lf\n" with start - 1 and finish - 1.
+ * "%lf" is glibc's in round-to-nearest: sign, integer digits, '.', six digits -- the decimal expansion of the exact binary
+ * value (f32 widened first), rounded half to even at the sixth decimal, computed in integers (csrc/wt_text.h);
+ * '-' whenever the sign bit is set (-0.0 prints -0.000000, and so does -1e-9); nan / -nan by the sign bit, inf / -inf.
+ * DEPARTURE: chromosome identity is the SEGMENT (the reference compares name pointers): two segments are two chromosomes
+ * even where their names are equal.
+ * WIDE VALUES.  Finite |v| >= 2^64 needs multi-word decimal conversion and is not printed on the device: the door counts them
+ * in *n_wide and, if there is any, returns WTAMD_ERR_ARG with nothing written; the caller prints that batch on the host.
+ * state (HOST, may be NULL: a fresh writer, nothing returned) chains the batches of one writer.
+ * WTAMD_ERR_ARG, NOTHING written to text and state untouched: an unknown flag bit; a name outside 1 .. 255 bytes; in_block
+ * outside 0 .. 9999; a run with start >= finish or start == INT32_MIN; fewer than 0 or at least 2^31 runs; any wide value.
+ * WTAMD_ERR_CAPACITY when the text needs more than `capacity`: *n_bytes receives the size needed, not one byte of text is
+ * written, state is untouched.  *n_bytes is always written on success; an empty call returns 0 bytes and leaves state untouched.
+ * One workgroup per block of the reference, two passes (measure, emit) around a scan of the blocks' sizes; no atomics on
+ * global memory: the same list gives the same bytes on every call.  Synchronous on `stream`; temporary memory from the device
+ * pool: 32 bytes per 10000 runs, 12 bytes and the name per segment, 64 bytes of scalars. */
+#define WTAMD_TEXT_BLOCK 10000
+#define WTAMD_TEXT_BEDGRAPH 1u
+typedef struct {            /* HOST, in / out: chains batches of one writer; all zero = a fresh writer            */
+    int32_t in_block;       /* entries already in the current block, 0 .. 9999; 0: the three below are ignored */
+    int32_t point_by_point; /* mode after the last entry                                                       */
+    int32_t last_finish;    /* finish of the last entry                                                        */
+    int32_t continues;      /* in: this call's first non-empty segment is the chromosome of the last entry;    */
+} wtamd_text_state;         /* out: 1 after a call with runs -- the caller clears it before a new chromosome   */
+int wtamd_runs_text(int64_t n_seg, const int64_t *seg_off, const char *const *seg_name,
+                    const int32_t *start, const int32_t *finish, const void *value, int value_is_f64,
+                    uint32_t flags, wtamd_text_state *state, char *text, int64_t capacity,
+                    int64_t *n_bytes, int64_t *n_wide, void *stream);
+/* The same over run lists held in HOST arrays, double values and a HOST text buffer: device memory, copies and the call on
+ * the null stream. */
+int wtamd_runs_text_host(int64_t n_seg, const int64_t *seg_off, const char *const *seg_name,
+                         const int32_t *start, const int32_t *finish, const double *value,
+                         uint32_t flags, wtamd_text_state *state, char *text, int64_t capacity,
+                         int64_t *n_bytes, int64_t *n_wide);
+
 /* Run compression on device (reference CompressionWiggleIterator, unaryOps.c:235-253, which the
  * default writer applies, wigWriter.c:263-267): adjacent runs of one chromosome merge while
  * start == previous finish and (both NaN or |value - value of the group's first run| < 1e-6).
@@ -975,6 +1023,23 @@ WiggleIterator *wtamd_EnergyIntegrator(WiggleIterator *child, int wavelength);
 /* n wavelengths from ONE drain of the child: reim[2 k], reim[2 k + 1] are what n integrators would hold as real and im, bit
  * for bit.  WTAMD_OK, or WTAMD_ERR_ARG for n < 1 or n above 1024. */
 int wtamd_EnergySpectrum(WiggleIterator *child, int n, const int *wavelengths, double *reim);
+/* The reference's writers, TeeWiggleIterator, toFile and toStdout (wigWriter.c:261-289; `write`, `write_bg`), on
+ * wtamd_runs_text: the same bytes in the file.  The iterator passes the runs it prints on, one per pop() and in blocks through
+ * wtamd_iterator_next_block.  bedGraph mode is forced for an overlapping child; otherwise the compression rule
+ * (unaryOps.c:235-253) goes in front -- a reducer of this library is asked for it (wtamd_iterator_compress_output), and the
+ * same rule runs on the host over every batch anyway, the open group carried across batches (the rule is idempotent) --, and
+ * the runs passed on are the compressed ones.  A batch (one block of a reducer, one chromosome of any other child) is
+ * formatted by wtamd_runs_text_host with a wtamd_text_state chaining the batches; a batch with a wide value,
+ * WTAMD_NO_DEVICE_TEXT=1 and a build of the drop-in layer without the HIP units use the host sweep (the same bytes).
+ * The text of a batch is written when all of its runs have been handed on (the next batch is fetched, or the child is
+ * exhausted), the block of 10000 entries it leaves open when that block is full or at the end.  holdFire: nothing is written
+ * before the first seek.  SEEK: the reference kills its writer thread and loses whatever it had not yet printed -- a race that
+ * cannot be reproduced; here the complete 10000-entry blocks of what was handed on are written, the open block is dropped
+ * (what the reference does when its thread keeps up), then fflush, the child is sought and the entry count restarts at 0.
+ * wtamd_toFile closes the file it opened (the reference leaves it to exit()). */
+WiggleIterator *wtamd_TeeWiggleIterator(WiggleIterator *wi, FILE *out, wt_bool bedGraph, wt_bool holdFire);
+void wtamd_toFile(WiggleIterator *wi, char *filename, wt_bool bedGraph, wt_bool holdFire);
+void wtamd_toStdout(WiggleIterator *wi, wt_bool bedGraph, wt_bool holdFire);
 /* BigWig reader: the role of the reference's BigWiggleReader (src/bigWiggleReader.c:147-151) on this
  * library's own section decoder -- chromosomes in strcmp order, 1-based starts, box != 0: intervals
  * cut at the reference reader's 10 000-bp stretch edges (what `write_bg` parity needs); one producer

@@ -233,6 +233,43 @@ def energy_spectrum(child, wavelengths):
     return out, out[:, 0] * out[:, 0] + out[:, 1] * out[:, 1]
 
 
+def _c_file(path, mode="w"):
+    libc = C.CDLL(None)
+    libc.fopen.restype = C.c_void_p
+    libc.fopen.argtypes = [C.c_char_p, C.c_char_p]
+    libc.fclose.argtypes = [C.c_void_p]
+    fp = libc.fopen(str(path).encode(), mode.encode())
+    if not fp:
+        raise OSError("could not open %s" % path)
+    return fp, (lambda: libc.fclose(fp))
+
+
+def tee_iterator(child, path, bedgraph=False, hold_fire=False):
+    """wtamd_TeeWiggleIterator: the reference's `write` / `write_bg` writer of `child` into the file at `path`, passing the
+    runs it prints on.  Returns (iterator, close): pop it to the end (drain_pops / drain_blocks), then call close()."""
+    L = _bind()
+    L.wtamd_TeeWiggleIterator.restype = C.c_void_p
+    L.wtamd_TeeWiggleIterator.argtypes = [C.c_void_p, C.c_void_p, C.c_char, C.c_char]
+    fp, close = _c_file(path)
+    return L.wtamd_TeeWiggleIterator(child, fp, b"\x01" if bedgraph else b"\x00", b"\x01" if hold_fire else b"\x00"), close
+
+
+def to_file(child, path, bedgraph=False, hold_fire=False):
+    """wtamd_toFile: the reference's toFile -- `child` run to its end, the text at `path`."""
+    L = _bind()
+    L.wtamd_toFile.restype = None
+    L.wtamd_toFile.argtypes = [C.c_void_p, C.c_char_p, C.c_char, C.c_char]
+    L.wtamd_toFile(child, str(path).encode(), b"\x01" if bedgraph else b"\x00", b"\x01" if hold_fire else b"\x00")
+
+
+def to_stdout(child, bedgraph=False, hold_fire=False):
+    """wtamd_toStdout: the reference's toStdout."""
+    L = _bind()
+    L.wtamd_toStdout.restype = None
+    L.wtamd_toStdout.argtypes = [C.c_void_p, C.c_char, C.c_char]
+    L.wtamd_toStdout(child, b"\x01" if bedgraph else b"\x00", b"\x01" if hold_fire else b"\x00")
+
+
 def bigwig_reader(path, box=True):
     """wtamd_BigWiggleReader: the reference's BigWiggleReader role (bigWiggleReader.c:147-151), bulk-capable."""
     return _bind().wtamd_BigWiggleReader(path.encode(), int(box))

@@ -372,6 +372,64 @@ def energy_runlists(rl: RunLists, wavelengths):
     return out
 
 
+TEXT_BEDGRAPH, TEXT_BLOCK = 1, 10000          # WTAMD_TEXT_*
+TEXT_CANARY = 0xC7
+
+
+class TextState(C.Structure):
+    """wtamd_text_state: chains the batches of one writer."""
+    _fields_ = [(k, C.c_int32) for k in ("in_block", "point_by_point", "last_finish", "continues")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+def _text_door(rl, flags=0, state=None, capacity=None, offset=0, names=None, seg_off=None, n_seg=None):
+    """wtamd_runs_text over every segment of `rl` (one track), in order.  Returns (rc, the whole buffer as a uint8 array,
+    n_bytes, n_wide, state after as a dict or None).  The text starts at byte `offset` of a device buffer of offset + capacity
+    + 64 bytes filled with TEXT_CANARY; capacity None: the size a first call with no room reports.  state: a dict of the
+    fields of wtamd_text_state, or None.  names: the segments' names as bytes (default: rl.chrom_names).  seg_off / n_seg: given
+    to the door in place of rl's own (the refusals).  n_bytes and n_wide start out as -1."""
+    import torch
+    dev = torch.device("cuda", torch.cuda.current_device())
+    assert rl.n_tracks == 1
+    names = [n.encode() if isinstance(n, str) else n for n in (rl.chrom_names if names is None else names)]
+    arr = (C.c_char_p * max(len(names), 1))(*names)
+    seg = np.ascontiguousarray(rl.seg_off if seg_off is None else seg_off, np.int64)
+    n_seg = len(names) if n_seg is None else int(n_seg)
+    s = torch.from_numpy(np.ascontiguousarray(rl.start, np.int32)).to(dev)
+    f = torch.from_numpy(np.ascontiguousarray(rl.finish, np.int32)).to(dev)
+    v = torch.from_numpy(np.ascontiguousarray(rl.value)).to(dev)
+    is64 = 1 if rl.value.dtype == np.float64 else 0
+    fn = _lib.lib().wtamd_runs_text
+    nb, nw = C.c_int64(-1), C.c_int64(-1)
+    if capacity is None:
+        st = TextState(**state) if state is not None else None
+        rc = fn(n_seg, seg.ctypes.data, arr, s.data_ptr(), f.data_ptr(), v.data_ptr(), is64, int(flags), C.byref(st) if st is not None else None,
+                None, 0, C.byref(nb), C.byref(nw), None)
+        capacity = max(int(nb.value), 0)
+        nb, nw = C.c_int64(-1), C.c_int64(-1)
+    buf = torch.full((offset + capacity + 64,), TEXT_CANARY, dtype=torch.uint8, device=dev)
+    st = TextState(**state) if state is not None else None
+    rc = fn(n_seg, seg.ctypes.data, arr, s.data_ptr(), f.data_ptr(), v.data_ptr(), is64, int(flags), C.byref(st) if st is not None else None,
+            buf.data_ptr() + offset, int(capacity), C.byref(nb), C.byref(nw), None)
+    return rc, buf.cpu().numpy(), int(nb.value), int(nw.value), (st.as_dict() if st is not None else None)
+
+
+def text_runlists(rl: RunLists, bedgraph=False, track=0):
+    """The reference's `write` / `write_bg` (printBlock of TeeWiggleIterator, src/wigWriter.c:55-119) of one track of `rl` on
+    device (wtamd_runs_text): the bytes of the file.  The list is printed as it is: the compression the reference's wig writer
+    puts in front is the caller's (wtamd_runs_compress).  A finite value of 2^64 or more is refused (include/wiggletools_amd.h)."""
+    t = int(track)
+    segs = [(int(rl.seg_off[c * rl.n_tracks + t]), int(rl.seg_off[c * rl.n_tracks + t + 1])) for c in range(rl.n_chrom)]
+    idx = np.concatenate([np.arange(a, b) for a, b in segs] + [np.zeros(0, np.int64)]).astype(np.int64)
+    one = RunLists(rl.n_chrom, 1, np.concatenate([[0], np.cumsum([b - a for a, b in segs])]), rl.start[idx], rl.finish[idx], rl.value[idx],
+                   [rl.defaults[t]], list(rl.chrom_names))
+    rc, buf, nb, _, _ = _text_door(one, TEXT_BEDGRAPH if bedgraph else 0)
+    _lib.check(rc)
+    return buf[:nb].tobytes()
+
+
 class TrackSet:
     """N tracks resident in HBM (wtamd_trackset)."""
 
