@@ -13,6 +13,10 @@ class WiggleIterator(C.Structure):
                 ("overlaps", C.c_char), ("default_value", C.c_double), ("append", C.c_void_p)]
 
 
+POP = C.CFUNCTYPE(None, C.c_void_p)
+SEEK = C.CFUNCTYPE(None, C.c_void_p, C.c_char_p, C.c_int, C.c_int)
+
+
 class DropIn:
     def __init__(self, path):
         L = self.L = C.CDLL(path)
@@ -42,6 +46,33 @@ class DropIn:
         self.keep.append((arr, so, s, f, v))            # the arrays are borrowed by the reader
         fn = self.L.wtamd_OverlappingArrayReader if overlapping else self.L.wtamd_ArrayReader
         return fn(len(names), arr, so.ctypes.data, s.ctypes.data, f.ctypes.data, v.ctypes.data, 0.0)
+
+    def popping(self, names, seg_off, start, finish, value, overlapping=False, default=0.0):
+        """A foreign iterator by the reference's protocol over the chromosomes `names`: a WiggleIterator whose pop is a
+        callback, double values, stable chromosome names.  It does not seek."""
+        wi = WiggleIterator()
+        state = {"j": 0}
+        n = len(start)
+        chrom = np.repeat(np.arange(len(names)), np.diff(np.asarray(seg_off, np.int64)))
+        cnames = [n_.encode() for n_ in names]
+
+        def pop(_):
+            j = state["j"]
+            if j >= n:
+                wi.done = b"\x01"
+                return
+            wi.chrom = cnames[chrom[j]]
+            wi.start, wi.finish, wi.value = int(start[j]), int(finish[j]), float(value[j])
+            state["j"] = j + 1
+
+        cb, sk = POP(pop), SEEK(lambda *_: None)
+        wi.done = b"\x00"
+        wi.overlaps = b"\x01" if overlapping else b"\x00"
+        wi.default_value = float(default)
+        wi.pop, wi.seek = C.cast(cb, C.c_void_p), C.cast(sk, C.c_void_p)
+        pop(None)
+        self.keep.append((wi, cb, sk, cnames))
+        return C.addressof(wi)
 
     def coverage(self, child):
         return self.L.wtamd_CoverageIterator(child)

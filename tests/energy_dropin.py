@@ -1,17 +1,14 @@
 """What tests/test_energy_dropin_host.py (the emulated drop-in library: the host sweep) and tests/test_energy_dropin_gpu.py (the
 product) share: a ctypes driver of wtamd_EnergyIntegrator and wtamd_EnergySpectrum over wtamd_ArrayReader /
-wtamd_OverlappingArrayReader children (the bulk path, float32 values) and over a popping child written here (the reference's
-protocol, double values) -- against the recorded fixtures: the exact values within the door's bound, the reference's recorded
-values within the reference's."""
+wtamd_OverlappingArrayReader children (the bulk path, float32 values) and over a popping child (cover_dropin.DropIn.popping:
+the reference's protocol, double values) -- against the recorded fixtures: the exact values within the door's bound, the
+reference's recorded values within the reference's."""
 import ctypes as C
 
 import numpy as np
 
 import cover_dropin
 import energy_model as M
-
-POP = C.CFUNCTYPE(None, C.c_void_p)
-SEEK = C.CFUNCTYPE(None, C.c_void_p, C.c_char_p, C.c_int, C.c_int)
 
 
 class EnergyView(C.Structure):
@@ -36,28 +33,7 @@ class DropIn(cover_dropin.DropIn):
     def popping_child(self, names, lists, overlapping):
         """A foreign iterator by the reference's protocol over several chromosomes: a WiggleIterator whose pop is a callback,
         double values, stable chromosome names."""
-        wi = cover_dropin.WiggleIterator()
-        state = {"j": 0}
-        n = len(lists.s)
-        chrom = np.repeat(np.arange(lists.n_seg), np.diff(lists.seg))
-        cnames = [n_.encode() for n_ in names]
-
-        def pop(_):
-            j = state["j"]
-            if j >= n:
-                wi.done = b"\x01"
-                return
-            wi.chrom = cnames[chrom[j]]
-            wi.start, wi.finish, wi.value = int(lists.s[j]), int(lists.f[j]), float(lists.v[j])
-            state["j"] = j + 1
-
-        cb, sk = POP(pop), SEEK(lambda *_: None)
-        wi.done = b"\x00"
-        wi.overlaps = b"\x01" if overlapping else b"\x00"
-        wi.pop, wi.seek = C.cast(cb, C.c_void_p), C.cast(sk, C.c_void_p)
-        pop(None)
-        self.keep.append((wi, cb, sk, cnames))
-        return C.addressof(wi)
+        return self.popping(names, lists.seg, lists.s, lists.f, lists.v, overlapping)
 
     def integrate(self, child, lam, seek=None):
         """(real, im, res, res before the end) of wtamd_EnergyIntegrator popped to its end; seek = (chrom, start, finish): sought
@@ -100,7 +76,7 @@ def check_dropin(D, fixtures, setenv=None):
         seek = (sk["chrom"], sk["start"], sk["finish"]) if sk else None
         bulk_ok = _f32_exact(child)                         # (the array readers hold float32 values)
         if seek is not None and not bulk_ok:
-            continue                                        # (the popping child written here does not seek)
+            continue                                        # (the popping child does not seek)
         make = (lambda: D.bulk_child(names, child, over)) if bulk_ok else (lambda: D.popping_child(names, child, over))
         for no_device in (("0", "1") if setenv else ("0",)):
             if setenv:

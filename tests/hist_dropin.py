@@ -1,16 +1,13 @@
 """What tests/test_hist_dropin_host.py (the emulated drop-in library: the host sweep) and tests/test_hist_gpu.py (the product)
 share: a ctypes driver of wtamd_histogram, wtamd_normalize_histogram and wtamd_print_histogram over wtamd_ArrayReader children
-(the bulk path, float32 values) and over a popping child written here (the reference's protocol, double values) -- against the
-recorded fixtures and the model."""
+(the bulk path, float32 values) and over a popping child (cover_dropin.DropIn.popping: the reference's protocol, double
+values) -- against the recorded fixtures and the model."""
 import ctypes as C
 
 import numpy as np
 
 import cover_dropin
 import hist_model as M
-
-POP = C.CFUNCTYPE(None, C.c_void_p)
-SEEK = C.CFUNCTYPE(None, C.c_void_p, C.c_char_p, C.c_int, C.c_int)
 
 
 class DropIn(cover_dropin.DropIn):
@@ -45,25 +42,7 @@ class DropIn(cover_dropin.DropIn):
 
     def popping_child(self, s, f, v):
         """A foreign iterator by the reference's protocol: a WiggleIterator whose pop is a callback, double values."""
-        wi = cover_dropin.WiggleIterator()
-        state = {"j": 0}
-        n = len(s)
-
-        def pop(_):
-            j = state["j"]
-            if j >= n:
-                wi.done = b"\x01"
-                return
-            wi.start, wi.finish, wi.value = int(s[j]), int(f[j]), float(v[j])
-            state["j"] = j + 1
-
-        cb, sk = POP(pop), SEEK(lambda *_: None)
-        wi.chrom = b"chr1"
-        wi.done = b"\x00"
-        wi.pop, wi.seek = C.cast(cb, C.c_void_p), C.cast(sk, C.c_void_p)
-        pop(None)
-        self.keep.append((wi, cb, sk))
-        return C.addressof(wi)
+        return self.popping(["chr1"], [0, len(s)], s, f, v)
 
     def printed(self, h):
         fp = self.libc.tmpfile()

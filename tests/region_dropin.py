@@ -148,7 +148,8 @@ def check_dropin(D, oracle, fixtures, rng):
         if overlapping:
             continue
         # Multiplexer children under MeanReduction against the oracle's `mean` over the model's lists (trim and overlaps of
-        # the same source, and noverlaps of another: values k / 8, which the f32 blocks hold exactly)
+        # the same source, and noverlaps of another: values k / 8, float32-exact, so the Multiplexer takes
+        # the served lists in float32 blocks; tests/compose_dropin.py serves lists that are not)
         other = random_case(rng, names, n_max, span, False)
         kids = [("trim", case), ("overlaps", case), ("noverlaps", other)]
         lists = []

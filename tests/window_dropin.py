@@ -106,16 +106,14 @@ def check_dropin(D, fixtures, setenv=None):
                 seen["seek"] += 1
             if np.isnan(case.v).any():
                 continue
-            # under a SumReduction of this library: the Multiplexer takes the iterators in blocks of float32 values
+            # under a SumReduction of this library: the Multiplexer takes the doubles the iterators pop
             kids = (C.c_void_p * 2)(make(), make())
             D.keep.append(kids)
             red = D.read_pops(D.L.SumReduction(D.L.newMultiplexer(kids, 2, b"\x00")))
             ok = [r for r in rows if r[3] == r[3]]
             if len(ok) == len(rows):
-                # (the Multiplexer takes an iterator's current element as the double it is and the rest of a chromosome in
-                # blocks of float32 values)
                 assert [r[:3] for r in red] == [r[:3] for r in rows], (c["name"], op, "reducer")
-                assert all(x[3] in (2.0 * r[3], 2.0 * float(np.float32(r[3]))) for x, r in zip(red, rows)), (c["name"], op, "reducer")
+                assert all(x[3] == 2.0 * r[3] for x, r in zip(red, rows)), (c["name"], op, "reducer")
                 seen["reducer"] += 1
             # over an overlapping child: the union comes first
             over = M.Case([(np.repeat(s, 2), np.stack([f, f + 1 + np.arange(len(f)) % 3]).T.ravel(), np.stack([v, v + 1]).T.ravel()) for s, f, v in case.chroms])

@@ -13,9 +13,6 @@
 // One combination never goes to the door: a trim whose SOURCE overlaps itself.  What the reference puts out then depends on
 // the order of its pops (it loses intersections), so the door refuses such a source and this iterator follows the
 // reference's own per-interval protocol on the host.
-//
-// Values: pop() and wtamd_iterator_next_block deliver f64.  The blocks the Multiplexer takes hold f32, as for every bulk
-// source: a `nearest` distance above 2^24 is rounded there.
 #ifndef WT_ABI_REGION_H_
 #define WT_ABI_REGION_H_
 

@@ -16,31 +16,6 @@ struct RegRuns {
     void push(int32_t a, int32_t b, double x) { s.push_back(a); f.push_back(b); v.push_back(x); }
 };
 
-// Every interval of the chromosome `it` stands on, in blocks where it is a bulk source; keep == NULL: skipped; values: false
-// leaves keep->v alone.
-void reg_drain_chrom(WiggleIterator *it, const char *chrom, RegRuns *keep, bool values = true) {
-    BulkSource *bulk = it->pop == &wt_bulk_pop ? (BulkSource *) it->data : nullptr;
-    while (!it->done && strcmp(it->chrom, chrom) == 0) {
-        const int32_t *bs, *bf;
-        const float *bv;
-        const int64_t cnt = bulk ? bulk->peek(bulk, &bs, &bf, &bv) : 0;
-        if (cnt > 0) {
-            if (keep) {
-                keep->s.insert(keep->s.end(), bs, bs + cnt);
-                keep->f.insert(keep->f.end(), bf, bf + cnt);
-                if (values) keep->v.insert(keep->v.end(), bv, bv + cnt);
-            }
-            bulk->advance(bulk, it, cnt);
-        } else {
-            if (keep) {
-                keep->s.push_back(it->start); keep->f.push_back(it->finish);
-                if (values) keep->v.push_back(it->value);
-            }
-            it->pop(it);
-        }
-    }
-}
-
 // the device door (a weak reference: absent in a build of this layer without the HIP units), unless <no_device_var>=1
 bool wt_use_device(const void *door, const char *no_device_var) {
     const char *e = getenv(no_device_var);
@@ -57,7 +32,8 @@ struct ServedRuns {
     void (*load)(ServedRuns *) = nullptr;
     const char *chrom = nullptr;    // interned name of the chromosome being served
     RegRuns out;
-    std::vector<float> vf;          // the values as float32 for the Multiplexer's blocks
+    std::vector<float> vf;          // the values as float32 for the Multiplexer's blocks: only where f32_exact
+    bool f32_exact = false;         // every value of `out` is a float32 (or NaN): decided once per load
     int64_t j = 0;
     bool done = false;
     bool block_out = false;         // wtamd_iterator_next_block handed out [j, end): the next call moves past it
@@ -68,7 +44,15 @@ void srv_settle(ServedRuns *c, WiggleIterator *wi) {
         c->out.clear(); c->vf.clear();
         c->j = 0;
         c->load(c);
+        // What a consumer sees is what pop() delivers, a double.  The float32 blocks are offered only for a chromosome whose
+        // values all are float32; any other goes run by run (srv_peek returns 0), or through its f64 arrays (reg_drain_chrom).
         c->vf.assign(c->out.v.begin(), c->out.v.end());
+        c->f32_exact = true;
+        for (size_t q = 0; q < c->vf.size() && c->f32_exact; q++) {
+            const double v = c->out.v[q];
+            c->f32_exact = (double) c->vf[q] == v || v != v;
+        }
+        if (!c->f32_exact) c->vf.clear();
     }
     if (c->done) { wi->done = 1; return; }
     wi->chrom = (char *) c->chrom;
@@ -78,7 +62,7 @@ void srv_settle(ServedRuns *c, WiggleIterator *wi) {
 
 int64_t srv_peek(BulkSource *b, const int32_t **s, const int32_t **f, const float **v) {
     ServedRuns *c = (ServedRuns *) b;
-    if (c->done || c->block_out || c->j >= (int64_t) c->out.s.size()) return 0;
+    if (c->done || c->block_out || !c->f32_exact || c->j >= (int64_t) c->out.s.size()) return 0;
     *s = c->out.s.data() + c->j; *f = c->out.f.data() + c->j; *v = c->vf.data() + c->j;
     return (int64_t) c->out.s.size() - c->j;
 }
@@ -129,6 +113,43 @@ int64_t srv_next_block(WiggleIterator *wi, const char **chrom, const int32_t **s
     *start = c->out.s.data() + c->j; *finish = c->out.f.data() + c->j; *value = c->out.v.data() + c->j;
     c->block_out = true;
     return n;
+}
+
+// Every interval of the chromosome `it` stands on, in blocks where it is a bulk source (a served run list: its f64 arrays, the
+// doubles its pop() delivers); keep == NULL: skipped; values: false leaves keep->v alone.
+void reg_drain_chrom(WiggleIterator *it, const char *chrom, RegRuns *keep, bool values = true) {
+    BulkSource *bulk = it->pop == &wt_bulk_pop ? (BulkSource *) it->data : nullptr;
+    ServedRuns *served = srv_is(it) ? (ServedRuns *) it->data : nullptr;
+    while (!it->done && strcmp(it->chrom, chrom) == 0) {
+        if (served && !served->block_out && served->j < (int64_t) served->out.s.size()) {
+            const RegRuns &o = served->out;
+            const int64_t cnt = (int64_t) o.s.size() - served->j;
+            if (keep) {
+                keep->s.insert(keep->s.end(), o.s.begin() + served->j, o.s.end());
+                keep->f.insert(keep->f.end(), o.f.begin() + served->j, o.f.end());
+                if (values) keep->v.insert(keep->v.end(), o.v.begin() + served->j, o.v.end());
+            }
+            srv_advance(&served->hdr, it, cnt);
+            continue;
+        }
+        const int32_t *bs, *bf;
+        const float *bv;
+        const int64_t cnt = bulk ? bulk->peek(bulk, &bs, &bf, &bv) : 0;
+        if (cnt > 0) {
+            if (keep) {
+                keep->s.insert(keep->s.end(), bs, bs + cnt);
+                keep->f.insert(keep->f.end(), bf, bf + cnt);
+                if (values) keep->v.insert(keep->v.end(), bv, bv + cnt);
+            }
+            bulk->advance(bulk, it, cnt);
+        } else {
+            if (keep) {
+                keep->s.push_back(it->start); keep->f.push_back(it->finish);
+                if (values) keep->v.push_back(it->value);
+            }
+            it->pop(it);
+        }
+    }
 }
 
 // ---------------------------------------------------------------------------
