@@ -13,16 +13,15 @@ to the exact value: span, covered, min and max bit for bit, the sum bit for bit 
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 
 import exact
+from model_common import _p  # noqa: F401
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(ROOT, "wiggletools_amd", "csrc")
-HEADER = os.path.join(CSRC, "wt_apply.h")
 
 OK, ERR_ARG = 0, 1
 STRICT = 1
@@ -266,24 +265,10 @@ def mid_size():
 
 
 # ---- the passes of csrc/wt_apply.h on the CPU (tests/apply_emu.cpp) ----
-_emu = None
-
-
 def emu_lib():
-    global _emu
-    if _emu is None:
-        so = os.path.join(HERE, "libapply_emu.so")
-        deps = [os.path.join(HERE, "apply_emu.cpp"), os.path.join(HERE, "emu", "runs_launcher.h"), HEADER] + [os.path.join(CSRC, h) for h in ("wt_region.h", "wt_cover.h", "wt_moments_merge.h")]
-        if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-            tmp = "%s.tmp.%d" % (so, os.getpid())
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Wno-unused-function", "-o", tmp, deps[0]])
-            os.replace(tmp, so)
-        _emu = C.CDLL(so)
-    return _emu
-
-
-def _p(a):
-    return C.c_void_p(a.ctypes.data)
+    """tests/emu/libwt_apply_emu.so, built (tests/emu/build.py) and loaded once."""
+    from emu import build
+    return build.load_unit("apply")
 
 
 def emu_apply(seg, s, f, v, rseg, rs, rf, default=0.0, strict=True, order=0, seed=0, flags=None):

@@ -9,13 +9,8 @@ removes it from recorded reference output and says how many it removed.
 Union: an interval joins the current group while group.finish > start (strict); the group has the first member's start and
 value and the largest finish."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 
 
 def coverage(start, finish):
@@ -124,20 +119,10 @@ def flat(segs):
 
 
 # ---- the passes of csrc/wt_cover.h on the CPU (tests/cover_emu.cpp) ----
-_emu = None
-
-
 def emu_lib():
-    global _emu
-    if _emu is None:
-        so = os.path.join(HERE, "libcover_emu.so")
-        deps = [os.path.join(HERE, "cover_emu.cpp"), os.path.join(HERE, "emu", "runs_launcher.h"), os.path.join(ROOT, "wiggletools_amd", "csrc", "wt_cover.h")]
-        if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-            tmp = "%s.tmp.%d" % (so, os.getpid())
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-function", "-o", tmp, deps[0]])
-            os.replace(tmp, so)
-        _emu = C.CDLL(so)
-    return _emu
+    """tests/emu/libwt_cover_emu.so, built (tests/emu/build.py) and loaded once."""
+    from emu import build
+    return build.load_unit("cover")
 
 
 def _out(cap):

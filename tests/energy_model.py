@@ -12,6 +12,8 @@ import re
 
 import numpy as np
 
+from model_common import _num, bits, same_bits  # noqa: F401
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "..", "wiggletools_amd", "csrc")
 HEADER = os.path.join(CSRC, "wt_energy.h")
@@ -130,15 +132,6 @@ def energy_bound(star, t):
     return 2 * (np.abs(star[:, 0]) + np.abs(star[:, 1])) * t + 2 * t * t
 
 
-def bits(x):
-    return np.ascontiguousarray(x, np.float64).view(np.uint64)
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a, np.float64), np.ascontiguousarray(b, np.float64)
-    return a.shape == b.shape and bool(((bits(a) == bits(b)) | (np.isnan(a) & np.isnan(b))).all())
-
-
 def check_close(got, star, n, S, what, c=DOOR_C):
     """got against the exact (n_wavelengths, 2): NaN where the model says NaN, exactly; otherwise inside the bound, and the
     energies inside theirs."""
@@ -154,10 +147,6 @@ def check_close(got, star, n, S, what, c=DOOR_C):
 
 
 # ---- recorded values ----
-def _num(x):
-    return float("nan") if x is None else float.fromhex(x) if isinstance(x, str) else float(x)
-
-
 def _hex(x):
     return None if x != x else float(x).hex()
 
@@ -227,29 +216,10 @@ def seam_values():
 
 
 # ---- the emulated passes and the host sweep ----
-_EMU = []
-
-
 def emu_lib():
-    """tests/emu/libwt_energy_emu.so: tests/energy_emu.cpp compiled with the emulator's flags, rebuilt when a source is newer."""
-    if not _EMU:
-        from emu import build
-        so = os.path.join(HERE, "emu", "libwt_energy_emu.so")
-        deps = [os.path.join(HERE, "energy_emu.cpp"), os.path.join(HERE, "emu", "runs_launcher.h"), HEADER, os.path.join(CSRC, "wt_cover.h")]
-        if not (os.path.exists(so) and all(os.path.getmtime(so) >= os.path.getmtime(d) for d in deps)):
-            build._compile(so, deps, [deps[0], "-lm"])
-        _EMU.append(C.CDLL(so))
-    return _EMU[0]
-
-
-def dropin_emu_lib():
-    """tests/emu/libwt_dropin_emu.so (the drop-in layer without the HIP units), rebuilt when the energy headers, which its own
-    dependency list does not name, are newer."""
+    """tests/emu/libwt_energy_emu.so, built (tests/emu/build.py) and loaded once."""
     from emu import build
-    so = os.path.join(HERE, "emu", "libwt_dropin_emu.so")
-    mine = [HEADER, os.path.join(CSRC, "wt_abi_energy.h")]
-    stale = os.path.exists(so) and any(os.path.getmtime(d) > os.path.getmtime(so) for d in mine)
-    return build.build_dropin(force=stale)
+    return build.load_unit("energy")
 
 
 def _p(x):

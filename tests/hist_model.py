@@ -11,6 +11,8 @@ import re
 
 import numpy as np
 
+from model_common import _num, _p, bits, same_bits  # noqa: F401
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "..", "wiggletools_amd", "csrc")
 HEADER = os.path.join(CSRC, "wt_hist.h")
@@ -144,20 +146,7 @@ def reference_equal(L, width):
     return bool(stream.min() >= min(a, b) and stream.max() <= max(a, b) and (width >= 2 or b > a))
 
 
-def bits(x):
-    return np.ascontiguousarray(x, np.float64).view(np.uint64)
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a, np.float64), np.ascontiguousarray(b, np.float64)
-    return a.shape == b.shape and bool(((bits(a) == bits(b)) | (np.isnan(a) & np.isnan(b))).all())
-
-
 # ---- fixtures ----
-def _num(x):
-    return float("nan") if x is None else float.fromhex(x) if isinstance(x, str) else float(x)
-
-
 def fixtures():
     return json.load(open(os.path.join(HERE, "golden", "hist_fixtures.json")))["cases"]
 
@@ -183,33 +172,10 @@ def all_fixtures_as_one():
 
 
 # ---- the emulated passes and the host sweep ----
-_EMU = []
-
-
 def emu_lib():
-    """tests/emu/libwt_hist_emu.so: tests/hist_emu.cpp compiled with the emulator's flags, rebuilt when a source is newer."""
-    if not _EMU:
-        from emu import build
-        so = os.path.join(HERE, "emu", "libwt_hist_emu.so")
-        deps = [os.path.join(HERE, "hist_emu.cpp"), os.path.join(HERE, "emu", "runs_launcher.h"), HEADER, os.path.join(CSRC, "wt_cover.h")]
-        if not (os.path.exists(so) and all(os.path.getmtime(so) >= os.path.getmtime(d) for d in deps)):
-            build._compile(so, deps, [deps[0], "-lm"])
-        _EMU.append(C.CDLL(so))
-    return _EMU[0]
-
-
-def dropin_emu_lib():
-    """tests/emu/libwt_dropin_emu.so (the drop-in layer without the HIP units), rebuilt when the histogram's headers, which its
-    own dependency list does not name, are newer."""
+    """tests/emu/libwt_hist_emu.so, built (tests/emu/build.py) and loaded once."""
     from emu import build
-    so = os.path.join(HERE, "emu", "libwt_dropin_emu.so")
-    mine = [HEADER, os.path.join(CSRC, "wt_abi_hist.h")]
-    stale = os.path.exists(so) and any(os.path.getmtime(d) > os.path.getmtime(so) for d in mine)
-    return build.build_dropin(force=stale)
-
-
-def _p(x):
-    return C.c_void_p(x.ctypes.data)
+    return build.load_unit("hist")
 
 
 def _call(fn, head, L, width, flags, given, base, dtype=None):

@@ -17,12 +17,12 @@ import ctypes.util
 import json
 import os
 import re
-import subprocess
 from fractions import Fraction
 
 import numpy as np
 
 import apply_model as AM
+from model_common import _p  # noqa: F401
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -339,25 +339,10 @@ def altered(case, s=None, f=None, rs=None, rf=None):
 
 
 # ---- the passes of csrc/wt_profile.h on the CPU (tests/profile_emu.cpp) ----
-_emu = None
-
-
 def emu_lib():
-    global _emu
-    if _emu is None:
-        so = os.path.join(HERE, "libprofile_emu.so")
-        deps = [os.path.join(HERE, "profile_emu.cpp"), os.path.join(HERE, "emu", "runs_launcher.h"), HEADER] + [os.path.join(CSRC, h) for h in ("wt_apply.h", "wt_region.h", "wt_cover.h", "wt_moments_merge.h")]
-        if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-            tmp = "%s.tmp.%d" % (so, os.getpid())
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas",
-                                   "-o", tmp, deps[0]])
-            os.replace(tmp, so)
-        _emu = C.CDLL(so)
-    return _emu
-
-
-def _p(a):
-    return C.c_void_p(a.ctypes.data)
+    """tests/emu/libwt_profile_emu.so, built (tests/emu/build.py) and loaded once."""
+    from emu import build
+    return build.load_unit("profile")
 
 
 def _out(case, W, flags):

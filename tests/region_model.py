@@ -12,7 +12,6 @@ trim_protocol is the reference's own pop protocol for a trim, which differs from
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 
@@ -182,20 +181,10 @@ def seam_cases():
 
 
 # ---- the passes of csrc/wt_region.h on the CPU (tests/region_emu.cpp) ----
-_emu = None
-
-
 def emu_lib():
-    global _emu
-    if _emu is None:
-        so = os.path.join(HERE, "libregion_emu.so")
-        deps = [os.path.join(HERE, "region_emu.cpp"), os.path.join(HERE, "emu", "runs_launcher.h"), HEADER, os.path.join(os.path.dirname(HEADER), "wt_cover.h")]
-        if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-            tmp = "%s.tmp.%d" % (so, os.getpid())
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-function", "-o", tmp, deps[0]])
-            os.replace(tmp, so)
-        _emu = C.CDLL(so)
-    return _emu
+    """tests/emu/libwt_region_emu.so, built (tests/emu/build.py) and loaded once."""
+    from emu import build
+    return build.load_unit("region")
 
 
 def default_capacity(op, n, m):

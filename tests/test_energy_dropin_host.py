@@ -4,7 +4,8 @@ included: the recorded exact values within the door's bound, the reference's rec
 giving NaN (tests/energy_dropin.py, which tests/test_energy_dropin_gpu.py runs over the product)."""
 import energy_dropin
 import energy_model as M
+from emu import build as emu_build
 
 
 def test_the_dropin_energy_on_the_host_sweep():
-    energy_dropin.check_dropin(energy_dropin.DropIn(M.dropin_emu_lib()), M.fixtures())
+    energy_dropin.check_dropin(energy_dropin.DropIn(emu_build.build_dropin()), M.fixtures())

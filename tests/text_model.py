@@ -346,29 +346,10 @@ def check_against_fixture(c, L, flags, txt):
 
 
 # ---- the emulated passes and the host sweep ----
-_EMU = []
-
-
 def emu_lib():
-    """tests/emu/libwt_text_emu.so: tests/text_emu.cpp compiled with the emulator's flags, rebuilt when a source is newer."""
-    if not _EMU:
-        from emu import build
-        so = os.path.join(HERE, "emu", "libwt_text_emu.so")
-        deps = [os.path.join(HERE, "text_emu.cpp"), os.path.join(HERE, "emu", "runs_launcher.h"), HEADER, os.path.join(CSRC, "wt_cover.h")]
-        if not (os.path.exists(so) and all(os.path.getmtime(so) >= os.path.getmtime(d) for d in deps)):
-            build._compile(so, deps, [deps[0], "-lm"])
-        _EMU.append(C.CDLL(so))
-    return _EMU[0]
-
-
-def dropin_emu_lib():
-    """tests/emu/libwt_dropin_emu.so (the drop-in layer without the HIP units), rebuilt when the text unit's headers, which its
-    own dependency list does not name, are newer."""
+    """tests/emu/libwt_text_emu.so, built (tests/emu/build.py) and loaded once."""
     from emu import build
-    so = os.path.join(HERE, "emu", "libwt_dropin_emu.so")
-    mine = [HEADER, os.path.join(CSRC, "wt_abi_text.h")]
-    stale = os.path.exists(so) and any(os.path.getmtime(d) > os.path.getmtime(so) for d in mine)
-    return build.build_dropin(force=stale)
+    return build.load_unit("text")
 
 
 def mergeable_list(n=700, seed=31):

@@ -9,15 +9,15 @@ Term) where Term carries the exact value, the sum of the |terms| that entered it
 the tests are made of.  Nothing here normalises a quirk: a gap inside a chromosome reads as 0 under smooth, the trailing phase
 drops one value per pop, bin tests the default's truth as C does (NaN counts, -0.0 does not)."""
 import ctypes as C
-import fcntl
 import json
 import math
 import os
 import re
-import subprocess
 from fractions import Fraction
 
 import numpy as np
+
+from model_common import _p  # noqa: F401
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -283,27 +283,10 @@ def seek_child(case, g, lo, hi):
 
 
 # ---- the plain-C++ passes and host sweeps ----
-_emu = None
-
-
 def emu_lib():
-    global _emu
-    if _emu is None:
-        so = os.path.join(HERE, "emu", "libwt_window_emu.so")
-        deps = [os.path.join(HERE, "window_emu.cpp"), os.path.join(HERE, "emu", "runs_launcher.h"), HEADER, os.path.join(CSRC, "wt_cover.h")]
-        with open(os.path.join(HERE, "emu", ".build.lock"), "w") as lk:
-            fcntl.flock(lk, fcntl.LOCK_EX)
-            if not (os.path.exists(so) and all(os.path.getmtime(so) >= os.path.getmtime(d) for d in deps)):
-                tmp = "%s.tmp.%d" % (so, os.getpid())
-                subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Wno-unused-function",
-                                       "-Wno-unknown-pragmas", "-o", tmp, deps[0]])
-                os.replace(tmp, so)
-        _emu = C.CDLL(so)
-    return _emu
-
-
-def _p(a):
-    return C.c_void_p(a.ctypes.data)
+    """tests/emu/libwt_window_emu.so, built (tests/emu/build.py) and loaded once."""
+    from emu import build
+    return build.load_unit("window")
 
 
 def _outputs(cap):
