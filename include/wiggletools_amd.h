@@ -728,6 +728,49 @@ int wtamd_runs_text_host(int64_t n_seg, const int64_t *seg_off, const char *cons
                          uint32_t flags, wtamd_text_state *state, char *text, int64_t capacity,
                          int64_t *n_bytes, int64_t *n_wide);
 
+/* Multi-column wig, bedGraph and paste text on device (csrc/wt_mtext.hip): the reference's Multiplexer writer, printBlock of
+ * TeeMultiplexer / PasteMultiplexer (src/mWigWriter.c:56-133; the parser's `mwrite`, `mwrite_bg`, `apply_paste`), byte for
+ * byte.  The layout of wtamd_runs_text plus a tile: values is a DEVICE array of n * width doubles, row r at values + r * width
+ * (a track that is not in play holds its default in the tile, as the materialising kernel writes it; inplay is not read).
+ * ROW(r) is, for every column, "\t" and "%lf" of the cell (wtamd_runs_text's "%lf"), then "\n".  Blocks of WTAMD_TEXT_BLOCK
+ * entries, the mode and the header rule are those of wtamd_runs_text.  A point-by-point entry prints its header (if any) and
+ * ROW(r) L times; any other entry prints "%s\t%i\t%i" (name, start - 1, finish - 1) and ROW(r): at width 1 the line
+ * wtamd_runs_text prints.  PASTE: with prefix (DEVICE bytes) and prefix_off (DEVICE, n + 1 offsets; both or neither) entry r
+ * prints its prefix bytes verbatim (0 bytes is legal) and ROW(r); the mode is bedGraph.  Chromosome identity is the segment.
+ * width runs from 1 to WTAMD_MTEXT_MAX_WIDTH.  A finite cell of 2^64 or more is counted in *n_wide and refused, as there.
+ * WTAMD_ERR_ARG, NOTHING written and state untouched: what wtamd_runs_text refuses (WTAMD_MTEXT_STRICT is an unknown flag
+ * here); a width outside the limits; one of prefix / prefix_off without the other; prefix offsets that decrease.
+ * WTAMD_ERR_CAPACITY, the state, the empty call and determinism: as wtamd_runs_text.  Four passes (cells, mode, scan, emit), no
+ * floating-point and no global atomics.  Synchronous on `stream`; temporary memory from the device pool: 4 bytes per entry, 8
+ * per 256 entries, 8 per 10000 entries, 4 per max(1, 2048 / width) entries, 12 bytes and the name per segment, 64 of scalars. */
+#define WTAMD_MTEXT_BEDGRAPH 1u
+#define WTAMD_MTEXT_STRICT 2u       /* wtamd_trackset_mtext only */
+#define WTAMD_MTEXT_MAX_WIDTH 65536
+int wtamd_tile_text(int64_t n_seg, const int64_t *seg_off, const char *const *seg_name,
+                    const int32_t *start, const int32_t *finish, const double *values, int32_t width,
+                    const char *prefix, const int64_t *prefix_off,
+                    uint32_t flags, wtamd_text_state *state, char *text, int64_t capacity,
+                    int64_t *n_bytes, int64_t *n_wide, void *stream);
+/* The same over HOST arrays (prefix and prefix_off included) and a HOST text buffer: device memory from the pool, copies and
+ * the call on the null stream. */
+int wtamd_tile_text_host(int64_t n_seg, const int64_t *seg_off, const char *const *seg_name,
+                         const int32_t *start, const int32_t *finish, const double *values, int32_t width,
+                         const char *prefix, const int64_t *prefix_off,
+                         uint32_t flags, wtamd_text_state *state, char *text, int64_t capacity,
+                         int64_t *n_bytes, int64_t *n_wide);
+/* `mwrite` / `mwrite_bg` of a resident track set: the Multiplexer tile is materialised on the device (the route of
+ * wtamd_multiplex_host; WTAMD_MTEXT_STRICT asks for WTAMD_STRICT_SET0) and printed by the passes above with the chromosomes
+ * as segments (chrom_name: HOST, n_chrom names of 1 .. 255 bytes); the tile never leaves HBM.  text: DEVICE memory.  *n_runs
+ * (may be NULL) receives the number of entries.  Device memory: what wtamd_multiplex_host allocates (16 bytes per run of
+ * wtamd_trackset_max_runs, 9 bytes per run and track, 8 per chromosome) plus the text passes' scratch.  A genome that does not
+ * fit is cut by the caller into track sets with range_lo / range_hi; `state` (HOST, may be NULL) chains the pieces' texts as
+ * in wtamd_runs_text -- the caller clears `continues` where a piece starts a new chromosome.  Synchronous. */
+int wtamd_trackset_mtext(wtamd_trackset *ts, const char *const *chrom_name, uint32_t flags, wtamd_text_state *state,
+                         char *text, int64_t capacity, int64_t *n_bytes, int64_t *n_wide, int64_t *n_runs, void *stream);
+/* The same into a HOST text buffer. */
+int wtamd_trackset_mtext_host(wtamd_trackset *ts, const char *const *chrom_name, uint32_t flags, wtamd_text_state *state,
+                              char *text, int64_t capacity, int64_t *n_bytes, int64_t *n_wide, int64_t *n_runs);
+
 /* Run compression on device (reference CompressionWiggleIterator, unaryOps.c:235-253, which the
  * default writer applies, wigWriter.c:263-267): adjacent runs of one chromosome merge while
  * start == previous finish and (both NaN or |value - value of the group's first run| < 1e-6).
@@ -1040,6 +1083,20 @@ int wtamd_EnergySpectrum(WiggleIterator *child, int n, const int *wavelengths, d
 WiggleIterator *wtamd_TeeWiggleIterator(WiggleIterator *wi, FILE *out, wt_bool bedGraph, wt_bool holdFire);
 void wtamd_toFile(WiggleIterator *wi, char *filename, wt_bool bedGraph, wt_bool holdFire);
 void wtamd_toStdout(WiggleIterator *wi, wt_bool bedGraph, wt_bool holdFire);
+/* The reference's Multiplexer writers, TeeMultiplexer, toStdoutMultiplexer and PasteMultiplexer (mWigWriter.c:179-327;
+ * `mwrite`, `mwrite_bg`, `apply_paste`), on wtamd_tile_text: the same bytes in the file.  The returned Multiplexer shares
+ * values / inplay / default_values with `in`, copies chrom / start / finish on every pop, records the entry and pops `in`; it
+ * is primed by one pop and works over any `in` (this library's Multiplexer, wtamd_ApplyMultiplexer, wtamd_ProfileMultiplexer,
+ * a foreign one).  Complete blocks of 10000 entries are formatted by wtamd_tile_text_host, several per call, and fwritten; the
+ * open block at the end.  WTAMD_NO_DEVICE_MTEXT=1, a batch with a wide value and a build of the drop-in layer without the HIP
+ * units use the host sweep (the same bytes).  Paste reads one line of `infile` per entry exactly as the reference does
+ * (fgets of 5000 bytes, empty / `track` / `browser` lines skipped, trailing \n and \r stripped; a file that runs out: what was
+ * recorded is written, then the reference's message and exit(1)).  SEEK and holdFire: as wtamd_TeeWiggleIterator -- complete
+ * blocks of what was handed on are written, the open block is dropped, fflush, `in` is sought, the count restarts.  The tile
+ * still comes home on this path (its callers read the struct); wtamd_trackset_mtext is the path on which it does not. */
+Multiplexer *wtamd_TeeMultiplexer(Multiplexer *in, FILE *out, wt_bool bedGraph, wt_bool holdFire);
+void wtamd_toStdoutMultiplexer(Multiplexer *in, wt_bool bedGraph, wt_bool holdFire);
+Multiplexer *wtamd_PasteMultiplexer(Multiplexer *in, FILE *infile, FILE *outfile, wt_bool holdFire);
 /* BigWig reader: the role of the reference's BigWiggleReader (src/bigWiggleReader.c:147-151) on this
  * library's own section decoder -- chromosomes in strcmp order, 1-based starts, box != 0: intervals
  * cut at the reference reader's 10 000-bp stretch edges (what `write_bg` parity needs); one producer

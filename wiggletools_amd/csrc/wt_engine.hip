@@ -1126,6 +1126,12 @@ int wtamd_multiplex_host(wtamd_trackset *ts, uint32_t flags, wtamd_runs *runs, d
     return wt_reduce_host_impl(ts, WT_OP_MULTIPLEX, flags, 0, runs, values, inplay, n_runs);
 }
 
+// the Multiplexer tile of the track set's current data into device arrays, on `s` (csrc/wt_mtext.hip prints it)
+extern "C++" int wt_multiplex_device(wtamd_trackset *ts, uint32_t flags, wtamd_runs *runs, double *d_tile, uint8_t *d_inplay, int64_t *n_runs,
+                                     hipStream_t s) {
+    return wt_reduce_impl(ts, WT_OP_MULTIPLEX, flags, 0, runs, d_tile, d_inplay, n_runs, s);
+}
+
 static int wt_runs_auc_span(const wtamd_runs *runs, int64_t n_runs, double *auc, double *span, void *stream) {
     hipStream_t s = (hipStream_t) stream;
     const int blocks = 512;

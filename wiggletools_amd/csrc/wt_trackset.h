@@ -107,4 +107,10 @@ int wt_reduce_enqueue(wtamd_trackset *ts, const wtamd_reduce_desc &desc, wtamd_r
 int wt_launch_patch(wtamd_trackset *ts, int delta_W, int op, uint32_t flags, int n_set0, wtamd_runs *runs, long long n_bad,
                     hipStream_t s);
 
+// The Multiplexer tile of the track set's current data (the route of wtamd_multiplex_host) into DEVICE arrays, on `s`:
+// runs (start, finish, value = the in-play count, chrom_run_off), d_tile[capacity * n_tracks], d_inplay likewise; *n_runs is
+// written when the launch is through.  flags: WTAMD_STRICT_SET0 or 0.
+int wt_multiplex_device(wtamd_trackset *ts, uint32_t flags, wtamd_runs *runs, double *d_tile, uint8_t *d_inplay, int64_t *n_runs,
+                        hipStream_t s);
+
 #endif  // WT_TRACKSET_H_

@@ -270,6 +270,39 @@ def to_stdout(child, bedgraph=False, hold_fire=False):
     L.wtamd_toStdout(child, b"\x01" if bedgraph else b"\x00", b"\x01" if hold_fire else b"\x00")
 
 
+def _flag(x):
+    return b"\x01" if x else b"\x00"
+
+
+def tee_multiplexer(multi, path, bedgraph=False, hold_fire=False):
+    """wtamd_TeeMultiplexer: the reference's `mwrite` / `mwrite_bg` writer of the Multiplexer `multi` into the file at `path`.
+    Returns (multiplexer, close): pop it to the end (popMultiplexer / runMultiplexer), then call close()."""
+    L = _bind()
+    L.wtamd_TeeMultiplexer.restype = C.c_void_p
+    L.wtamd_TeeMultiplexer.argtypes = [C.c_void_p, C.c_void_p, C.c_char, C.c_char]
+    fp, close = _c_file(path)
+    return L.wtamd_TeeMultiplexer(multi, fp, _flag(bedgraph), _flag(hold_fire)), close
+
+
+def to_stdout_multiplexer(multi, bedgraph=False, hold_fire=False):
+    """wtamd_toStdoutMultiplexer: the reference's toStdoutMultiplexer."""
+    L = _bind()
+    L.wtamd_toStdoutMultiplexer.restype = None
+    L.wtamd_toStdoutMultiplexer.argtypes = [C.c_void_p, C.c_char, C.c_char]
+    L.wtamd_toStdoutMultiplexer(multi, _flag(bedgraph), _flag(hold_fire))
+
+
+def paste_multiplexer(multi, in_path, out_path, hold_fire=False):
+    """wtamd_PasteMultiplexer: the reference's `apply_paste` writer -- every entry of `multi` behind the next line of the file
+    at `in_path`, into the file at `out_path`.  Returns (multiplexer, close)."""
+    L = _bind()
+    L.wtamd_PasteMultiplexer.restype = C.c_void_p
+    L.wtamd_PasteMultiplexer.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char]
+    fin, close_in = _c_file(in_path, "r")
+    fout, close_out = _c_file(out_path)
+    return L.wtamd_PasteMultiplexer(multi, fin, fout, _flag(hold_fire)), (lambda: (close_out(), close_in()))
+
+
 def bigwig_reader(path, box=True):
     """wtamd_BigWiggleReader: the reference's BigWiggleReader role (bigWiggleReader.c:147-151), bulk-capable."""
     return _bind().wtamd_BigWiggleReader(path.encode(), int(box))

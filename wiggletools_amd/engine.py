@@ -430,6 +430,68 @@ def text_runlists(rl: RunLists, bedgraph=False, track=0):
     return buf[:nb].tobytes()
 
 
+MTEXT_BEDGRAPH, MTEXT_STRICT, MTEXT_MAX_WIDTH = 1, 2, 65536          # WTAMD_MTEXT_*
+
+
+def _mtext_door(names, seg_off, start, finish, values, prefixes=None, flags=0, state=None, capacity=None, offset=0, width=None, prefix_mode="both",
+                host=False):
+    """wtamd_tile_text (host=True: wtamd_tile_text_host) over a tile: names (bytes or str, one per segment), seg_off, start /
+    finish (n), values (n x width float64), prefixes (None, or n bytes objects: paste).  Returns what _text_door returns.  width:
+    given to the door in place of the tile's own; prefix_mode "prefix" / "off": only that one of prefix / prefix_off is given
+    (the refusals)."""
+    import torch
+    names = [n.encode() if isinstance(n, str) else n for n in names]
+    arr = (C.c_char_p * max(len(names), 1))(*names)
+    seg = np.ascontiguousarray(seg_off, np.int64)
+    s, f = np.ascontiguousarray(start, np.int32), np.ascontiguousarray(finish, np.int32)
+    v = np.ascontiguousarray(values, np.float64).reshape(len(s), -1) if len(s) else np.zeros((0, max(int(width or 1), 1)))
+    pre = off = None
+    if prefixes is not None:
+        off = np.zeros(len(s) + 1, np.int64)
+        off[1:] = np.cumsum([len(p) for p in prefixes])
+        pre = np.frombuffer(b"".join(prefixes) + b"\0", np.uint8).copy()
+    w = int(v.shape[1] if width is None else width)
+    if host:
+        fn, tail = _lib.lib().wtamd_tile_text_host, ()
+        ptr = lambda a: a.ctypes.data if a is not None else None       # noqa: E731
+        keep = (s, f, v, pre, off)
+    else:
+        dev = torch.device("cuda", torch.cuda.current_device())
+        fn, tail = _lib.lib().wtamd_tile_text, (None,)
+        keep = tuple(torch.from_numpy(a).to(dev) if a is not None else None for a in (s, f, v, pre, off))
+        ptr = lambda t: t.data_ptr() if t is not None else None        # noqa: E731
+    ps, pf, pv, pp, po = (ptr(a) for a in keep)
+    if prefix_mode == "prefix":
+        po = None
+    if prefix_mode == "off":
+        pp = None
+
+    def once(text_ptr, cap):
+        st = TextState(**state) if state is not None else None
+        nb, nw = C.c_int64(-1), C.c_int64(-1)
+        rc = fn(len(names), seg.ctypes.data, arr, ps, pf, pv, w, pp, po, int(flags), C.byref(st) if st is not None else None, text_ptr, int(cap),
+                C.byref(nb), C.byref(nw), *tail)
+        return rc, int(nb.value), int(nw.value), (st.as_dict() if st is not None else None)
+
+    if capacity is None:
+        capacity = max(once(None, 0)[1], 0)
+    if host:
+        buf = np.full(offset + capacity + 64, TEXT_CANARY, np.uint8)
+        rc, nb, nw, st = once(buf.ctypes.data + offset, capacity)
+        return rc, buf, nb, nw, st
+    buf = torch.full((offset + capacity + 64,), TEXT_CANARY, dtype=torch.uint8, device=dev)
+    rc, nb, nw, st = once(buf.data_ptr() + offset, capacity)
+    return rc, buf.cpu().numpy(), nb, nw, st
+
+
+def tile_text(names, seg_off, start, finish, values, prefixes=None, bedgraph=False):
+    """The reference's `mwrite` / `mwrite_bg` / paste text (printBlock of TeeMultiplexer, src/mWigWriter.c:56-133) of a tile on
+    the device (wtamd_tile_text): the bytes of the file.  values: n x width; prefixes: one bytes object per entry (paste)."""
+    rc, buf, nb, _, _ = _mtext_door(names, seg_off, start, finish, values, prefixes, MTEXT_BEDGRAPH if bedgraph else 0)
+    _lib.check(rc)
+    return buf[:nb].tobytes()
+
+
 class TrackSet:
     """N tracks resident in HBM (wtamd_trackset)."""
 
@@ -552,6 +614,25 @@ class TrackSet:
         n = n.value
         chrom = np.repeat(np.arange(self.n_chrom, dtype=np.int32), np.diff(cro))
         return chrom, s[:n].copy(), f[:n].copy(), tile[:n].copy(), ip[:n].copy()
+
+    def mtext(self, chrom_names, bedgraph=False, strict=False, state=None):
+        """The file `mwrite` / `mwrite_bg` would write for this track set (wtamd_trackset_mtext_host): the tile is materialised
+        and printed on the device, only the text comes home.  state: a TextState to chain pieces of a genome, or None."""
+        names = [n.encode() if isinstance(n, str) else n for n in chrom_names]
+        assert len(names) == self.n_chrom
+        arr = (C.c_char_p * max(len(names), 1))(*names)
+        flags = (MTEXT_BEDGRAPH if bedgraph else 0) | (MTEXT_STRICT if strict else 0)
+        fn = _lib.lib().wtamd_trackset_mtext_host
+        nb, nw, nr = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        sp = C.byref(state) if state is not None else None
+        rc = fn(self._h, arr, flags, sp, None, 0, C.byref(nb), C.byref(nw), C.byref(nr))
+        if rc == 3:                             # WTAMD_ERR_CAPACITY: nb holds the size
+            buf = np.empty(nb.value, np.uint8)
+            rc = fn(self._h, arr, flags, sp, buf.ctypes.data, len(buf), C.byref(nb), C.byref(nw), C.byref(nr))
+            _lib.check(rc)
+            return buf[:nb.value].tobytes()
+        _lib.check(rc)
+        return b""
 
     # ---- device-resident path (bench, pipelines) ----
     def alloc_runs(self, capacity=None):
