@@ -771,6 +771,84 @@ int wtamd_trackset_mtext(wtamd_trackset *ts, const char *const *chrom_name, uint
 int wtamd_trackset_mtext_host(wtamd_trackset *ts, const char *const *chrom_name, uint32_t flags, wtamd_text_state *state,
                               char *text, int64_t capacity, int64_t *n_bytes, int64_t *n_wide, int64_t *n_runs);
 
+/* Wig, bedGraph and BED text INTO run lists on the device (csrc/wt_read.hip; csrc/wt_read.h is the single source of the rule):
+ * the inverse of wtamd_runs_text, the reference's WiggleReader (src/wigReader.c) and BedReader (src/bedReader.c) over the bytes
+ * of a file.  text: DEVICE memory, n_bytes of WHOLE LINES at any alignment: the last byte is '\n', unless WTAMD_READ_EOF is set
+ * for a file's unterminated last line; anything else is WTAMD_ERR_ARG.  state (HOST, in / out, all zero at the start of a file)
+ * carries from one chunk to the next: the reading mode, span, step and the start of the next fixedStep line, the last record's
+ * start, the latest header's chromosome and -- DEPARTURE from one name: a header may name a chromosome no record has yet, so
+ * `continues` needs its own -- the last record's name (each: length and up to 255 bytes).
+ * THE RULE.  Every line is one of
+ *   skipped  the first byte is '#', or the line begins with "track" (wigReader.c:153-165); any bytes may follow.
+ *   header   "fixedStep" or "variableStep", then key=value tokens, each after a single space or tab.  fixedStep takes chrom,
+ *            start, step (all three compulsory) and optionally span; variableStep takes chrom and optionally span; a key at most
+ *            once; span restarts at 1 with every header (wigReader.c:47).  A header sets the mode, the chromosome and, for
+ *            fixedStep, the position of the first data line.  A chrom value holds no '=' (the reference's strtok cuts there);
+ *            one that ENDS the header line keeps the line's '\n' in the name, as the reference's strtok leaves it: the name's
+ *            length includes it ("variableStep chrom=chr1\n" names "chr1\n"), and 255 bytes is the limit with it.
+ *   data     fields separated by exactly one space or tab, nothing leading or trailing (the reference's countWords: 1 + the
+ *            separator bytes).  4 fields `name int int number`: the record (name, a + 1, b + 1, v); it sets the mode to
+ *            bedGraph.  2 fields `int number`: (chrom, p, p + span, v), regular only while the latest mode setter is a
+ *            variableStep header.  1 field `number`: the k-th data line after a fixedStep header (k from 0) is (chrom, start +
+ *            k step, that + span, v), regular only while the latest setter is a fixedStep header.  Skipped lines do not count.
+ * With WTAMD_READ_BED (bedReader.c:41-52) every line that is not "#..." is name, blanks (spaces or tabs, one or more), int,
+ * blanks, int, then anything, and gives (name, a + 1, b + 1, 1.0); a record that sorts before its predecessor (strcmp of the
+ * names below zero, or equal names and a lower start) is counted in n_unsorted and the call is refused.
+ * An `int` is an optional '-', then 0 or a decimal without a leading zero, inside int32 after the + 1 / + span (the reference's
+ * %i reads 010 as 8 and 0x10 as 16: those are irregular).  A `number` is an optional '-', digits with an optional '.' and
+ * digits (or '.' digits), an optional e|E[+-] and 1 to 3 digits; or exactly nan, -nan, inf, -inf.  A name is 1 to 255 bytes
+ * above 0x20.  Everything else is IRREGULAR: a '\r', an empty line, a line of 4999 bytes or more (fgets(5000) would split it),
+ * a double separator, an unknown or repeated header key, step or span below 1, a keyword followed by something else than a
+ * space or tab, a coordinate outside int32.  Irregular lines are counted and the byte offset of the first is reported; if there
+ * is any the call returns WTAMD_ERR_ARG, writes nothing to the arrays and leaves the state untouched (with irregular lines only
+ * n_lines, n_irregular and first_irregular of counts are defined); the host sweep (wtr_host) reads the same rule on the host.
+ * VALUES, bit for bit strtod's.  W = the number's digits without leading zeros and without the fraction's trailing zeros, E
+ * the decimal exponent that goes with it.  W = 0 gives +-0.  W <= 2^53 and |E| <= 22: (double) W * 10^E or (double) W / 10^-E
+ * from a table of the 23 exact powers, ONE correctly rounded operation (Clinger's fast path) -- every line wtamd_runs_text
+ * prints for |v| < 9.0e9 ("%lf" has six decimals: beyond that W passes 2^53 unless they end in zeros).
+ * Any other regular number is SLOW: its record index and the byte offset of its number go to slow_rec /
+ * slow_off in record order, its value is written as NaN and the caller patches it with strtod (the _host door does).
+ * SEGMENTS.  Records come out in line order, one per data line.  A record opens a segment when it is the call's first or its
+ * name differs bytewise from the previous record's.  seg_off (DEVICE, seg_capacity + 1 entries; seg_off[n_seg] = n_runs)
+ * holds each segment's first record, seg_name_off / seg_name_len (seg_capacity entries) the name's byte offset in text and its
+ * length; an offset of -1 is the chromosome of the state that came in (a header of an earlier chunk); no other negative
+ * offset is ever written (the state's last record's name is compared inside the passes only).  counts->continues: the
+ * first record's name is the name of the incoming state's last record.  The door does not compress, merge or sort.
+ * WTAMD_ERR_CAPACITY: counts holds what is needed (n_runs, n_seg, n_slow); nothing written, state untouched.  An empty call
+ * leaves the state alone.  Unknown flag bits: WTAMD_ERR_ARG.  Six passes (lines, scan, count, scan2, write, state) of one
+ * kernel, no atomics on global memory, no floating-point reduction: the same text gives the same bytes.  Synchronous on
+ * `stream`; temporary memory from the device pool: 112 bytes per 4096 bytes of text, 1088 of states, 128 of scalars. */
+#define WTAMD_READ_BED 1u
+#define WTAMD_READ_EOF 2u
+#define WTAMD_READ_BEDGRAPH_MODE 0
+#define WTAMD_READ_FIXED_MODE 1
+#define WTAMD_READ_VARIABLE_MODE 2
+typedef struct {            /* HOST, in / out: chains the chunks of one file; all zero = the start of a file  */
+    int32_t mode;           /* WTAMD_READ_*_MODE: the latest mode setter                                       */
+    int32_t span, step;     /* of the latest header                                                            */
+    int32_t last_start;     /* of the last record                                                              */
+    int64_t next;           /* the start of the next fixedStep line                                            */
+    int32_t chrom_len;      /* bytes of chrom                                                                  */
+    int32_t rec_len;        /* bytes of rec_name; 0: no record yet                                             */
+    char chrom[256];        /* the latest header's chromosome                                                  */
+    char rec_name[256];     /* the last record's name                                                          */
+} wtamd_read_state;         /* 544 bytes                                                                       */
+typedef struct {
+    int64_t n_lines, n_runs, n_seg, n_slow, n_irregular, first_irregular /* -1: none */, n_unsorted, continues;
+} wtamd_read_counts;
+int wtamd_text_runs(const char *text, int64_t n_bytes, uint32_t flags, wtamd_read_state *state,
+                    int32_t *start, int32_t *finish, double *value, int64_t capacity,
+                    int64_t *seg_off, int64_t *seg_name_off, int32_t *seg_name_len, int64_t seg_capacity,
+                    int64_t *slow_rec, int64_t *slow_off, int64_t slow_capacity,
+                    wtamd_read_counts *counts, void *stream);
+/* The same over a HOST text buffer and HOST outputs, the slow values patched by strtod; seg_name (may be NULL) receives the
+ * names one after the other, seg_name_cap bytes in all, each closed by a 0 byte (a name taken from the incoming state
+ * included): WTAMD_ERR_CAPACITY when they do not fit.  Device memory from the pool, copies and the call on the null stream. */
+int wtamd_text_runs_host(const char *text, int64_t n_bytes, uint32_t flags, wtamd_read_state *state,
+                         int32_t *start, int32_t *finish, double *value, int64_t capacity,
+                         int64_t *seg_off, int64_t *seg_name_off, int32_t *seg_name_len, int64_t seg_capacity,
+                         char *seg_name, int64_t seg_name_cap, wtamd_read_counts *counts);
+
 /* Run compression on device (reference CompressionWiggleIterator, unaryOps.c:235-253, which the
  * default writer applies, wigWriter.c:263-267): adjacent runs of one chromosome merge while
  * start == previous finish and (both NaN or |value - value of the group's first run| < 1e-6).
@@ -1097,6 +1175,18 @@ void wtamd_toStdout(WiggleIterator *wi, wt_bool bedGraph, wt_bool holdFire);
 Multiplexer *wtamd_TeeMultiplexer(Multiplexer *in, FILE *out, wt_bool bedGraph, wt_bool holdFire);
 void wtamd_toStdoutMultiplexer(Multiplexer *in, wt_bool bedGraph, wt_bool holdFire);
 Multiplexer *wtamd_PasteMultiplexer(Multiplexer *in, FILE *infile, FILE *outfile, wt_bool holdFire);
+
+/* The reference's text readers (csrc/wt_abi_read.h): WiggleReader (src/wigReader.c: wig fixedStep / variableStep and bedGraph,
+ * its compression rule behind it, overlaps false, default 0) and BedReader (src/bedReader.c: value 1, overlaps true).  Served
+ * run lists: bulk sources to this library's Multiplexer and to wtamd_iterator_next_block, one run per pop() to anything else.
+ * The file is read in chunks cut at the last newline (WTAMD_READ_CHUNK_MB, default 64) through wtamd_text_runs_host, a
+ * wtamd_read_state chaining them; WTAMD_NO_DEVICE_READ=1, a build without the HIP units, and every chunk from the first one the
+ * door refuses on (an irregular line, an unsorted BED record) are read as the reference reads them: sscanf / strtok, its
+ * messages and exit(1) ("Badly formatted ...", "Invalid header ...", "Bed file ... is not sorted!"), fgets(5000) pieces.
+ * seek follows WiggleReaderSeek / BedReaderSeek; the file is reopened for it.  "-" reads stdin forwards; DEPARTURE: any seek on
+ * it ends as the reference's failed fopen does (the reference can seek stdin forwards). */
+WiggleIterator *wtamd_WiggleReader(char *path);
+WiggleIterator *wtamd_BedReader(char *path);
 /* BigWig reader: the role of the reference's BigWiggleReader (src/bigWiggleReader.c:147-151) on this
  * library's own section decoder -- chromosomes in strcmp order, 1-based starts, box != 0: intervals
  * cut at the reference reader's 10 000-bp stretch edges (what `write_bg` parity needs); one producer

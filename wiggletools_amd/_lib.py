@@ -113,6 +113,10 @@ def lib():
     L.wtamd_trackset_mtext.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                        C.POINTER(C.c_int64), C.c_void_p]
     L.wtamd_trackset_mtext_host.argtypes = L.wtamd_trackset_mtext.argtypes[:-1]
+    L.wtamd_text_runs.argtypes = [C.c_void_p, C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.wtamd_text_runs_host.argtypes = [C.c_void_p, C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
     L.wtamd_apply_finish.argtypes = [C.c_void_p, C.c_int]
     L.wtamd_apply_finish.restype = C.c_double
     L.wtamd_map_default.argtypes = [C.c_int, C.c_double, C.c_double]

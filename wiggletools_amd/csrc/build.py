@@ -7,7 +7,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SO = os.path.join(HERE, "libwiggletools_amd.so")
 # the kernel units (wt_kernels.h): the heavy compiles, one thread each
 KERNEL_SRCS = ["wt_reduce_stream.hip", "wt_reduce_moments.hip", "wt_reduce_order.hip", "wt_patch_kernels.hip", "wt_delta_kernels.hip", "wt_walk.hip"]
-SRCS = KERNEL_SRCS + ["wt_engine.hip", "wt_pool.hip", "wt_pipe.hip", "wt_compress.hip", "wt_moments.hip", "wt_map.hip", "wt_cover.hip", "wt_region.hip", "wt_apply.hip", "wt_profile.hip", "wt_window.hip", "wt_hist.hip", "wt_energy.hip", "wt_text.hip", "wt_mtext.hip", "wt_synth.hip", "wt_bwdev.hip", "wt_defaults.cpp", "wt_iter_abi.cpp", "wt_bigwig.cpp", "wt_bwwrite.cpp"]
+SRCS = KERNEL_SRCS + ["wt_engine.hip", "wt_pool.hip", "wt_pipe.hip", "wt_compress.hip", "wt_moments.hip", "wt_map.hip", "wt_cover.hip", "wt_region.hip", "wt_apply.hip", "wt_profile.hip", "wt_window.hip", "wt_hist.hip", "wt_energy.hip", "wt_text.hip", "wt_mtext.hip", "wt_read.hip", "wt_synth.hip", "wt_bwdev.hip", "wt_defaults.cpp", "wt_iter_abi.cpp", "wt_bigwig.cpp", "wt_bwwrite.cpp"]
 LIBS = ["-lz"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
          "-Wall", "-Wno-unused-function", "-Wno-pass-failed"]

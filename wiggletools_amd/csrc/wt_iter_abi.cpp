@@ -138,6 +138,7 @@ void wt_bulk_pop(WiggleIterator *wi) {
 #include "wt_abi_energy.h"
 #include "wt_abi_text.h"
 #include "wt_abi_mtext.h"
+#include "wt_abi_read.h"
 #include "wt_abi_bwdev.h"
 #include "wt_abi_ops.h"
 #include "wt_abi_integrators.h"

@@ -303,6 +303,23 @@ def paste_multiplexer(multi, in_path, out_path, hold_fire=False):
     return L.wtamd_PasteMultiplexer(multi, fin, fout, _flag(hold_fire)), (lambda: (close_out(), close_in()))
 
 
+def wiggle_reader(path):
+    """wtamd_WiggleReader: the reference's WiggleReader (wig fixedStep / variableStep and bedGraph text, compressed behind the
+    reader), its chunks parsed on the device; bulk-capable."""
+    L = _bind()
+    L.wtamd_WiggleReader.restype = C.c_void_p
+    L.wtamd_WiggleReader.argtypes = [C.c_char_p]
+    return L.wtamd_WiggleReader(str(path).encode())
+
+
+def bed_reader(path):
+    """wtamd_BedReader: the reference's BedReader (value 1, overlapping), its chunks parsed on the device; bulk-capable."""
+    L = _bind()
+    L.wtamd_BedReader.restype = C.c_void_p
+    L.wtamd_BedReader.argtypes = [C.c_char_p]
+    return L.wtamd_BedReader(str(path).encode())
+
+
 def bigwig_reader(path, box=True):
     """wtamd_BigWiggleReader: the reference's BigWiggleReader role (bigWiggleReader.c:147-151), bulk-capable."""
     return _bind().wtamd_BigWiggleReader(path.encode(), int(box))

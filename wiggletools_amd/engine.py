@@ -492,6 +492,100 @@ def tile_text(names, seg_off, start, finish, values, prefixes=None, bedgraph=Fal
     return buf[:nb].tobytes()
 
 
+READ_BED, READ_EOF = 1, 2          # WTAMD_READ_*
+READ_CANARY = 0x5C
+
+
+class ReadState(C.Structure):
+    """wtamd_read_state: chains the chunks of one file; all zero at its start."""
+    _fields_ = [("mode", C.c_int32), ("span", C.c_int32), ("step", C.c_int32), ("last_start", C.c_int32), ("next", C.c_int64),
+                ("chrom_len", C.c_int32), ("rec_len", C.c_int32), ("chrom", C.c_char * 256), ("rec_name", C.c_char * 256)]
+
+    def as_dict(self):
+        return {"mode": int(self.mode), "span": int(self.span), "step": int(self.step), "last_start": int(self.last_start), "next": int(self.next),
+                "chrom": self.chrom[:self.chrom_len], "rec_name": self.rec_name[:self.rec_len]}
+
+    @classmethod
+    def from_dict(cls, d):
+        st = cls()
+        if d:
+            st.mode, st.span, st.step, st.last_start, st.next = d["mode"], d["span"], d["step"], d["last_start"], d["next"]
+            st.chrom_len, st.rec_len = len(d["chrom"]), len(d["rec_name"])
+            st.chrom, st.rec_name = d["chrom"], d["rec_name"]
+        return st
+
+
+class ReadCounts(C.Structure):
+    """wtamd_read_counts."""
+    _fields_ = [(k, C.c_int64) for k in ("n_lines", "n_runs", "n_seg", "n_slow", "n_irregular", "first_irregular", "n_unsorted", "continues")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+def _read_door(data, flags=0, state=None, capacity=None, seg_capacity=None, slow_capacity=None, offset=0):
+    """wtamd_text_runs over `data` (bytes), which is copied to byte `offset` of a device allocation.  Returns a dict: rc, counts,
+    state (after, as a dict), and the whole of every output array as numpy (start, finish, value as uint64 bits, seg_off,
+    seg_name_off, seg_name_len, slow_rec, slow_off), each `capacity` entries (seg_off: seg_capacity + 1) with 8 canary entries of
+    READ_CANARY bytes on either side (key + "_lo" / "_hi" hold the guards' bytes).  A capacity None: the count a first call with
+    no room reports.  counts start out as -1."""
+    import torch
+    dev = torch.device("cuda", torch.cuda.current_device())
+    fn = _lib.lib().wtamd_text_runs
+    raw = np.frombuffer(bytes(data), np.uint8)
+    text = torch.full((offset + len(raw) + 64,), READ_CANARY, dtype=torch.uint8, device=dev)
+    if len(raw):
+        text[offset:offset + len(raw)] = torch.from_numpy(raw.copy()).to(dev)
+    if capacity is None or seg_capacity is None or slow_capacity is None:
+        st, cn = ReadState.from_dict(state), ReadCounts()
+        fn(text.data_ptr() + offset, len(raw), int(flags), C.addressof(st), None, None, None, 0, None, None, None, 0, None, None, 0, C.addressof(cn), None)
+        capacity = max(int(cn.n_runs), 0) if capacity is None else capacity
+        seg_capacity = max(int(cn.n_seg), 0) if seg_capacity is None else seg_capacity
+        slow_capacity = max(int(cn.n_slow), 0) if slow_capacity is None else slow_capacity
+    G = 8
+    sizes = {"start": (capacity, torch.int32), "finish": (capacity, torch.int32), "value": (capacity, torch.int64), "seg_off": (seg_capacity + 1, torch.int64),
+             "seg_name_off": (seg_capacity, torch.int64), "seg_name_len": (seg_capacity, torch.int32), "slow_rec": (slow_capacity, torch.int64),
+             "slow_off": (slow_capacity, torch.int64)}
+    bufs = {k: torch.full(((n + 2 * G) * dt.itemsize,), READ_CANARY, dtype=torch.uint8, device=dev).view(dt) for k, (n, dt) in sizes.items()}
+    ptr = lambda k: bufs[k].data_ptr() + G * sizes[k][1].itemsize      # noqa: E731
+    st, cn = ReadState.from_dict(state), ReadCounts(*([-1] * 8))
+    rc = fn(text.data_ptr() + offset, len(raw), int(flags), C.addressof(st), ptr("start"), ptr("finish"), ptr("value"), int(capacity), ptr("seg_off"),
+            ptr("seg_name_off"), ptr("seg_name_len"), int(seg_capacity), ptr("slow_rec"), ptr("slow_off"), int(slow_capacity), C.addressof(cn), None)
+    out = {"rc": rc, "counts": cn.as_dict(), "state": st.as_dict()}
+    for k, (n, dt) in sizes.items():
+        a = bufs[k].cpu().numpy()
+        out[k] = a[G:G + n].view(np.uint64) if k == "value" else a[G:G + n]
+        out[k + "_lo"], out[k + "_hi"] = a[:G].view(np.uint8), a[G + n:].view(np.uint8)
+    out["text_guard"] = text[offset + len(raw):].cpu().numpy()
+    return out
+
+
+def read_text(data: bytes, bed=False) -> RunLists:
+    """The reference's WiggleReader (wig fixedStep / variableStep and bedGraph; bed=True: BedReader, value 1) over the bytes of
+    a whole file on the device (wtamd_text_runs_host): one track, a chromosome per distinct name in order of first appearance
+    (a file that comes back to a chromosome is refused, as a RunLists cannot hold it), f64 values bit for bit strtod's.
+    The list is as the lines give it: the reference's reader compresses behind itself (wtamd_runs_compress does that).
+    Irregular text (include/wiggletools_amd.h) raises WtamdError."""
+    data = bytes(data)
+    flags = (READ_BED if bed else 0) | (READ_EOF if data and not data.endswith(b"\n") else 0)
+    fn = _lib.lib().wtamd_text_runs_host
+    st, cn = ReadState(), ReadCounts()
+    n = data.count(b"\n") + 1
+    s, f, v = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.float64)
+    seg, noff, nlen = np.zeros(n + 1, np.int64), np.zeros(n, np.int64), np.zeros(n, np.int32)
+    names = C.create_string_buffer(max(len(data), 1) + 257 * 2)
+    _lib.check(fn(data, len(data), flags, C.addressof(st), s.ctypes.data, f.ctypes.data, v.ctypes.data, n, seg.ctypes.data, noff.ctypes.data,
+                  nlen.ctypes.data, n, C.addressof(names), len(names), C.addressof(cn)))
+    m, g = int(cn.n_runs), int(cn.n_seg)
+    chrom, p = [], 0
+    for k in range(g):
+        chrom.append(names.raw[p:p + int(nlen[k])].decode("latin-1"))
+        p += int(nlen[k]) + 1
+    if len(set(chrom)) != len(chrom):
+        raise _lib.WtamdError("read_text: the text comes back to a chromosome it has left")
+    return RunLists(g, 1, np.concatenate([seg[:g], [m]]).astype(np.int64), s[:m].copy(), f[:m].copy(), v[:m].copy(), [0.0], chrom)
+
+
 class TrackSet:
     """N tracks resident in HBM (wtamd_trackset)."""
 
