@@ -396,7 +396,8 @@ WiggleIterator *wtamd_MapIterator(WiggleIterator *child, int map_op, double para
  * bigBed: the reference's readers with `overlaps = true`) into the non-overlapping tracks everything else here consumes.
  * Input in the layout of wtamd_runs_map: start / finish (and value, f32 or f64) are DEVICE arrays, seg_off / o_seg_off HOST
  * arrays of n_seg + 1 offsets; inside a segment the intervals are sorted by start (finishes in any order) and
- * start < finish -- anything else: WTAMD_ERR_ARG, nothing written.  The o_* arrays are DEVICE memory of `capacity` runs;
+ * start < finish -- anything else: WTAMD_ERR_ARG, nothing written (wtamd_runs_coverage_flags takes a segment's intervals in any
+ * order).  The o_* arrays are DEVICE memory of `capacity` runs;
  * when the result does not fit: WTAMD_ERR_CAPACITY with *n_out = the count needed.  Synchronous on `stream`.
  *
  * wtamd_runs_coverage -- the reference's CoverageWiggleIterator (src/unaryOps.c:303-375, the `coverage` command): per
@@ -414,6 +415,18 @@ WiggleIterator *wtamd_MapIterator(WiggleIterator *child, int map_op, double para
 int wtamd_runs_coverage(int64_t n_seg, const int64_t *seg_off, const int32_t *start, const int32_t *finish,
                         int64_t capacity, int32_t *o_start, int32_t *o_finish, double *o_value,
                         int64_t *o_seg_off, int64_t *n_out, void *stream);
+/* wtamd_runs_coverage with flags; flags 0 is wtamd_runs_coverage itself, results and errors alike.  A bit that is not listed
+ * here: WTAMD_ERR_ARG.
+ *   WTAMD_COVER_ANY_ORDER   the intervals of a segment may come in any order (the covering components of spliced reads in file
+ *                           order: after 50M1000N50M at 100 the next read's start at 120 follows an interval that starts at
+ *                           1150).  start >= finish is still refused.  The result is the coverage of the same intervals sorted
+ *                           by start, byte for byte, whole segments and segments cut at positions alike: a segment's extent is
+ *                           the integer minimum of its starts and maximum of its finishes, and every pass places an interval by
+ *                           its own start and finish alone.  Same scratch, same passes, no sort. */
+#define WTAMD_COVER_ANY_ORDER 1u
+int wtamd_runs_coverage_flags(int64_t n_seg, const int64_t *seg_off, const int32_t *start, const int32_t *finish,
+                              int64_t capacity, int32_t *o_start, int32_t *o_finish, double *o_value,
+                              int64_t *o_seg_off, int64_t *n_out, uint32_t flags, void *stream);
 int wtamd_runs_union(int64_t n_seg, const int64_t *seg_off, const int32_t *start, const int32_t *finish,
                      const void *value, int value_is_f64, int64_t capacity,
                      int32_t *o_start, int32_t *o_finish, double *o_value,
@@ -422,6 +435,9 @@ int wtamd_runs_union(int64_t n_seg, const int64_t *seg_off, const int32_t *start
  * chromosome): device memory, copies and the call on the null stream. */
 int wtamd_runs_coverage_host(int64_t n, const int32_t *start, const int32_t *finish, int64_t capacity, int32_t *o_start,
                              int32_t *o_finish, double *o_value, int64_t *n_out);
+/* The same over wtamd_runs_coverage_flags. */
+int wtamd_runs_coverage_host_flags(int64_t n, const int32_t *start, const int32_t *finish, int64_t capacity, int32_t *o_start,
+                                   int32_t *o_finish, double *o_value, int64_t *n_out, uint32_t flags);
 
 /* Region operators on device (csrc/wt_region.hip): the reference's OverlapWiggleIterator, NoverlapWiggleIterator,
  * TrimWiggleIterator and NearestWiggleIterator (src/unaryOps.c:437-639; the parser's `overlaps`, `noverlaps`, `trim`,

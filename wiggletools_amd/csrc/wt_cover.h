@@ -10,7 +10,10 @@
 // workgroup: whatever crosses workgroups crosses a kernel boundary (two-level scans as three kernels).
 //
 // Input (the layout of wtamd_runs_map): n_seg segments, seg_off[n_seg + 1], start / finish; inside a segment the intervals
-// are sorted by start and start < finish.
+// are sorted by start and start < finish.  Coverage with WCV_ANY_ORDER takes a segment's intervals in any order (what the
+// covering components of spliced reads are): only the pre-pass looks at the order -- its check, which the flag switches off;
+// a segment's extent is the minimum of its starts and the maximum of its finishes, both by integer atomics; every other pass
+// places an interval by its own start and finish alone, whole segments and pieces alike.
 //
 // COVERAGE of one segment.  B = the sorted distinct starts and finishes; run [B[k], B[k+1]) with value
 // #(start <= B[k]) - #(finish <= B[k]) wherever that is > 0 (runs are NOT merged where the depth does not change, as the
@@ -37,6 +40,7 @@
 #define WCV_BLOCK 256
 #define WCV_PER_LANE 8
 #define WCV_TILE (WCV_BLOCK * WCV_PER_LANE)      // items (bitmap words, breakpoints, intervals) one workgroup ranks / scans
+#define WCV_ANY_ORDER 1u                         // coverage flag (WTAMD_COVER_ANY_ORDER): a segment's intervals in any order
 
 #ifdef WT_EMU
 #define WCV_DEV inline
@@ -45,6 +49,7 @@
 WCV_DEV void wcv_or64(unsigned long long *p, unsigned long long v) { *p |= v; }
 WCV_DEV void wcv_add32(int *p, int v) { *p += v; }
 WCV_DEV void wcv_max32(int *p, int v) { if (v > *p) *p = v; }
+WCV_DEV void wcv_min32(int *p, int v) { if (v < *p) *p = v; }
 WCV_DEV void wcv_add64(long long *p, long long v) { *p += v; }
 WCV_DEV int wcv_popc(unsigned long long x) { return __builtin_popcountll(x); }
 #else
@@ -55,6 +60,7 @@ WCV_DEV int wcv_popc(unsigned long long x) { return __builtin_popcountll(x); }
 WCV_DEV void wcv_or64(unsigned long long *p, unsigned long long v) { atomicOr(p, v); }
 WCV_DEV void wcv_add32(int *p, int v) { atomicAdd(p, v); }
 WCV_DEV void wcv_max32(int *p, int v) { atomicMax(p, v); }
+WCV_DEV void wcv_min32(int *p, int v) { atomicMin(p, v); }
 WCV_DEV void wcv_add64(long long *p, long long v) { atomicAdd((unsigned long long *) p, (unsigned long long) v); }
 WCV_DEV int wcv_popc(unsigned long long x) { return __popcll(x); }
 #endif
@@ -71,6 +77,7 @@ struct WcvLds {
     unsigned int u[WCV_BLOCK];
     int acc;
     int same;
+    int lo;
 };
 
 // One record for every pass (each reads what it needs); device pointers unless said otherwise.
@@ -91,7 +98,8 @@ struct WcvArgs {
     long long t_cap;
     long long *dblk, *pblk;         // [breakpoint blocks] depth before the block / emitted runs before the block
     long long *scalars;
-    int32_t *segmax, *segmin;       // [n_seg] largest finish, first start (pre-pass)
+    int32_t *segmax, *segmin;       // [n_seg] largest finish, smallest start (pre-pass)
+    int any_order;                  // the pre-pass does not ask for starts in order
     // single-workgroup scans
     long long *scan;
     long long scan_n;
@@ -120,13 +128,14 @@ WCV_DEV long long wcv_seg_of(const int64_t *seg_off, long long n_seg, long long 
     return lo;
 }
 
-// ---- pre-pass: validation + the first start and the largest finish of every segment (one lane per interval) ----
+// ---- pre-pass: validation + the smallest start and the largest finish of every segment (one lane per interval) ----
 WCV_DEV void wcv_pre_block(const WcvArgs &a, long long block, WcvLds *lds) {
     const long long b0 = a.i0 + block * WCV_BLOCK;
     const long long last = (b0 + WCV_BLOCK <= a.i1 ? b0 + WCV_BLOCK : a.i1) - 1;
     WCV_LANES(l) {
         if (l == 0) {
             lds->acc = INT32_MIN;
+            lds->lo = INT32_MAX;
             // the whole workgroup in one segment (nearly always): one atomic per workgroup, not one per lane
             lds->same = wcv_seg_of(a.seg_off, a.n_seg, b0) == wcv_seg_of(a.seg_off, a.n_seg, last);
         }
@@ -138,15 +147,18 @@ WCV_DEV void wcv_pre_block(const WcvArgs &a, long long block, WcvLds *lds) {
         const long long g = wcv_seg_of(a.seg_off, a.n_seg, i);
         const int32_t s = a.start[i], f = a.finish[i];
         bool bad = s >= f;
-        if (i > (long long) a.seg_off[g] && a.start[i - 1] > s) bad = true;
+        if (!a.any_order && i > (long long) a.seg_off[g] && a.start[i - 1] > s) bad = true;
         if (bad) wcv_add64(&a.scalars[WCV_S_ERR], 1);
-        if (i == (long long) a.seg_off[g]) a.segmin[g] = s;
-        if (lds->same) wcv_max32(&lds->acc, f);
-        else wcv_max32(&a.segmax[g], f);
+        if (lds->same) { wcv_max32(&lds->acc, f); wcv_min32(&lds->lo, s); }
+        else { wcv_max32(&a.segmax[g], f); wcv_min32(&a.segmin[g], s); }
     }
     WCV_SYNC();
     WCV_LANES(l) {
-        if (l == 0 && lds->same) wcv_max32(&a.segmax[wcv_seg_of(a.seg_off, a.n_seg, b0)], lds->acc);
+        if (l == 0 && lds->same) {
+            const long long g = wcv_seg_of(a.seg_off, a.n_seg, b0);
+            wcv_max32(&a.segmax[g], lds->acc);
+            wcv_min32(&a.segmin[g], lds->lo);
+        }
     }
 }
 
@@ -369,7 +381,7 @@ WCV_DEV void wcv_segoff_block(const WcvArgs &a, long long block, WcvLds *) {
     WCV_LANES(l) {
         const long long g = a.seg_a + block * WCV_BLOCK + l;
         if (g >= a.seg_b || a.seg_off[g] == a.seg_off[g + 1]) continue;
-        const long long w = a.bbase[g] >> 6;                                // the segment's first start is bit 0 of this word
+        const long long w = a.bbase[g] >> 6;                                // the segment's smallest start is bit 0 of this word
         const long long r0 = a.blk[w / WCV_TILE] + (long long) a.wrank[w];
         const long long b = r0 / WCV_TILE;
         long long o = a.pblk[b];
@@ -600,12 +612,13 @@ static int wcv_cover_pass(L &l, WcvArgs a, long long n_bits, long long *n_emitte
     return 0;
 }
 
-// wtamd_runs_coverage.  budget: bytes of bitmap + word ranks (12 per 64 positions) one pass may hold.
+// wtamd_runs_coverage_flags.  budget: bytes of bitmap + word ranks (12 per 64 positions) one pass may hold.
 template <class L>
-static int wcv_coverage(L &l, long long n_seg, const int64_t *seg_off, const int32_t *start, const int32_t *finish, long long capacity,
-                        int32_t *o_start, int32_t *o_finish, double *o_value, int64_t *o_seg_off, int64_t *n_out, long long budget,
-                        const char **why) {
+static int wcv_coverage_flags(L &l, long long n_seg, const int64_t *seg_off, const int32_t *start, const int32_t *finish, long long capacity,
+                              int32_t *o_start, int32_t *o_finish, double *o_value, int64_t *o_seg_off, int64_t *n_out, long long budget,
+                              unsigned int flags, const char **why) {
     *why = "";
+    if (flags & ~WCV_ANY_ORDER) { *why = "unknown flag"; return 1; }
     if (n_seg < 0 || !seg_off || !o_seg_off || !n_out || capacity < 0) { *why = "bad argument"; return 1; }
     for (long long g = 0; g < n_seg; g++) if (seg_off[g + 1] < seg_off[g]) { *why = "segment offsets decrease"; return 1; }
     const long long n = n_seg ? (long long) (seg_off[n_seg] - seg_off[0]) : 0;
@@ -616,14 +629,16 @@ static int wcv_coverage(L &l, long long n_seg, const int64_t *seg_off, const int
     WcvArgs a = {};
     a.start = start; a.finish = finish; a.n_seg = n_seg; a.capacity = capacity;
     a.o_start = o_start; a.o_finish = o_finish; a.o_value = o_value; a.patch = -1;
+    a.any_order = (flags & WCV_ANY_ORDER) != 0;
     int64_t *d_seg = nullptr;
     long long *d_tab = nullptr;
     if (!sc.get(&d_seg, (size_t) n_seg + 1) || !sc.get(&a.segmax, (size_t) n_seg) || !sc.get(&a.segmin, (size_t) n_seg) || !sc.get(&a.scalars, (size_t) WCV_S_N) ||
         !sc.get(&a.o_seg, (size_t) n_seg + 1) || !sc.get(&d_tab, (size_t) n_seg * 3))
         { *why = "device memory"; return 2; }
     a.seg_off = d_seg;
-    std::vector<int32_t> h_max((size_t) n_seg, INT32_MIN), h_min((size_t) n_seg, 0);
+    std::vector<int32_t> h_max((size_t) n_seg, INT32_MIN), h_min((size_t) n_seg, INT32_MAX);
     if (!l.to_device(d_seg, seg_off, sizeof(int64_t) * ((size_t) n_seg + 1)) || !l.to_device(a.segmax, h_max.data(), sizeof(int32_t) * (size_t) n_seg) ||
+        !l.to_device(a.segmin, h_min.data(), sizeof(int32_t) * (size_t) n_seg) ||
         !l.zero(a.scalars, sizeof(long long) * WCV_S_N) || !l.zero(a.o_seg, sizeof(int64_t) * ((size_t) n_seg + 1)))
         { *why = "copy"; return 2; }
     // pre-pass: validation, the extent of every segment
@@ -632,7 +647,10 @@ static int wcv_coverage(L &l, long long n_seg, const int64_t *seg_off, const int
     if (!l.run(WCV_K_PRE, wcv_blocks(n, WCV_BLOCK), a) || !l.to_host(h_sc, a.scalars, sizeof h_sc) ||
         !l.to_host(h_max.data(), a.segmax, sizeof(int32_t) * (size_t) n_seg) || !l.to_host(h_min.data(), a.segmin, sizeof(int32_t) * (size_t) n_seg))
         { *why = "pre-pass"; return 2; }
-    if (h_sc[WCV_S_ERR]) { *why = "a segment is not sorted by start, or holds an interval with start >= finish"; return 1; }
+    if (h_sc[WCV_S_ERR]) {
+        *why = a.any_order ? "a segment holds an interval with start >= finish" : "a segment is not sorted by start, or holds an interval with start >= finish";
+        return 1;
+    }
     if ((capacity > 0 && (!o_start || !o_finish || !o_value))) { *why = "bad argument"; return 1; }
     const long long budget_words = budget / 12 > 1 ? budget / 12 : 1;
     std::vector<long long> tab((size_t) n_seg * 3, 0);      // wlo | whi | bbase
@@ -690,6 +708,14 @@ static int wcv_coverage(L &l, long long n_seg, const int64_t *seg_off, const int
     for (long long q = n_seg - 1; q >= 0; q--) if (seg_off[q + 1] == seg_off[q]) o_seg_off[q] = o_seg_off[q + 1];
     *n_out = out;
     return out > capacity ? 3 : 0;
+}
+
+// wtamd_runs_coverage: every segment sorted by start
+template <class L>
+static int wcv_coverage(L &l, long long n_seg, const int64_t *seg_off, const int32_t *start, const int32_t *finish, long long capacity,
+                        int32_t *o_start, int32_t *o_finish, double *o_value, int64_t *o_seg_off, int64_t *n_out, long long budget,
+                        const char **why) {
+    return wcv_coverage_flags(l, n_seg, seg_off, start, finish, capacity, o_start, o_finish, o_value, o_seg_off, n_out, budget, 0u, why);
 }
 
 // wtamd_runs_union

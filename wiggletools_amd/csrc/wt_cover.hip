@@ -59,13 +59,19 @@ bool wt_cover_run(void *stream, int kernel, long long blocks, const WcvArgs &a) 
 
 extern "C" {
 
-int wtamd_runs_coverage(int64_t n_seg, const int64_t *seg_off, const int32_t *start, const int32_t *finish, int64_t capacity,
-                        int32_t *o_start, int32_t *o_finish, double *o_value, int64_t *o_seg_off, int64_t *n_out, void *stream) {
+int wtamd_runs_coverage_flags(int64_t n_seg, const int64_t *seg_off, const int32_t *start, const int32_t *finish, int64_t capacity,
+                              int32_t *o_start, int32_t *o_finish, double *o_value, int64_t *o_seg_off, int64_t *n_out, uint32_t flags,
+                              void *stream) {
     HipLauncher l{{(hipStream_t) stream, nullptr}};
     const char *why = "";
-    const int rc = wcv_coverage(l, (long long) n_seg, seg_off, start, finish, (long long) capacity, o_start, o_finish, o_value, o_seg_off,
-                                n_out, wcv_budget(), &why);
-    return wt_runs_report("wtamd_runs_coverage", rc, why);
+    const int rc = wcv_coverage_flags(l, (long long) n_seg, seg_off, start, finish, (long long) capacity, o_start, o_finish, o_value,
+                                      o_seg_off, n_out, wcv_budget(), flags, &why);
+    return wt_runs_report(flags ? "wtamd_runs_coverage_flags" : "wtamd_runs_coverage", rc, why);
+}
+
+int wtamd_runs_coverage(int64_t n_seg, const int64_t *seg_off, const int32_t *start, const int32_t *finish, int64_t capacity,
+                        int32_t *o_start, int32_t *o_finish, double *o_value, int64_t *o_seg_off, int64_t *n_out, void *stream) {
+    return wtamd_runs_coverage_flags(n_seg, seg_off, start, finish, capacity, o_start, o_finish, o_value, o_seg_off, n_out, 0u, stream);
 }
 
 int wtamd_runs_union(int64_t n_seg, const int64_t *seg_off, const int32_t *start, const int32_t *finish, const void *value,
@@ -79,8 +85,8 @@ int wtamd_runs_union(int64_t n_seg, const int64_t *seg_off, const int32_t *start
 }
 
 // One segment in HOST memory in, its depth track in HOST memory out (what wtamd_CoverageIterator calls per chromosome).
-int wtamd_runs_coverage_host(int64_t n, const int32_t *start, const int32_t *finish, int64_t capacity, int32_t *o_start,
-                             int32_t *o_finish, double *o_value, int64_t *n_out) {
+int wtamd_runs_coverage_host_flags(int64_t n, const int32_t *start, const int32_t *finish, int64_t capacity, int32_t *o_start,
+                                   int32_t *o_finish, double *o_value, int64_t *n_out, uint32_t flags) {
     if (n < 0 || !n_out || (n > 0 && (!start || !finish))) return wt_fail(WTAMD_ERR_ARG, "wtamd_runs_coverage_host: bad argument");
     *n_out = 0;
     if (n == 0) return WTAMD_OK;
@@ -95,7 +101,7 @@ int wtamd_runs_coverage_host(int64_t n, const int32_t *start, const int32_t *fin
         return wt_fail(WTAMD_ERR_HIP, "wtamd_runs_coverage_host: out of device memory");
     const int64_t seg[2] = {0, n};
     int64_t oseg[2] = {0, 0};
-    const int rc = wtamd_runs_coverage(1, seg, in.start, in.finish, cap, d_out, d_out + cap, d_val, oseg, n_out, nullptr);
+    const int rc = wtamd_runs_coverage_flags(1, seg, in.start, in.finish, cap, d_out, d_out + cap, d_val, oseg, n_out, flags, nullptr);
     if (rc != WTAMD_OK) return rc;
     if (*n_out > capacity) return wt_fail(WTAMD_ERR_CAPACITY, "wtamd_runs_coverage_host: the output arrays are too small (*n_out holds the count needed)");
     if (*n_out > 0) {
@@ -104,6 +110,11 @@ int wtamd_runs_coverage_host(int64_t n, const int32_t *start, const int32_t *fin
         WT_HIP(hipMemcpy(o_value, d_val, sizeof(double) * (size_t) *n_out, hipMemcpyDeviceToHost));
     }
     return WTAMD_OK;
+}
+
+int wtamd_runs_coverage_host(int64_t n, const int32_t *start, const int32_t *finish, int64_t capacity, int32_t *o_start,
+                             int32_t *o_finish, double *o_value, int64_t *n_out) {
+    return wtamd_runs_coverage_host_flags(n, start, finish, capacity, o_start, o_finish, o_value, n_out, 0u);
 }
 
 }  // extern "C"

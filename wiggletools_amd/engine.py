@@ -61,8 +61,12 @@ def map_runlists(rl: RunLists, op, param=0.0):
     return RunLists(rl.n_chrom, rl.n_tracks, oseg, os_[:m].cpu().numpy(), of[:m].cpu().numpy(), ov[:m].cpu().numpy(), d)
 
 
-def _overlap_door(rl, union, capacity=None):
-    """wtamd_runs_coverage / wtamd_runs_union over every segment of `rl`; returns (rc, runs needed, RunLists or None)."""
+COVER_ANY_ORDER = 1      # WTAMD_COVER_ANY_ORDER
+
+
+def _overlap_door(rl, union, capacity=None, flags=None):
+    """wtamd_runs_coverage / wtamd_runs_union over every segment of `rl`; returns (rc, runs needed, RunLists or None).
+    flags (coverage only): not None goes through wtamd_runs_coverage_flags."""
     import torch
     dev = torch.device("cuda", torch.cuda.current_device())
     n = int(rl.seg_off[-1])
@@ -81,9 +85,12 @@ def _overlap_door(rl, union, capacity=None):
         v = torch.from_numpy(np.ascontiguousarray(rl.value)).to(dev)
         rc = L.wtamd_runs_union(n_seg, seg.ctypes.data, s.data_ptr(), f.data_ptr(), v.data_ptr(), 1 if rl.value.dtype == np.float64 else 0,
                                 cap, os_.data_ptr(), of.data_ptr(), ov.data_ptr(), oseg.ctypes.data, C.byref(n_out), None)
-    else:
+    elif flags is None:
         rc = L.wtamd_runs_coverage(n_seg, seg.ctypes.data, s.data_ptr(), f.data_ptr(), cap, os_.data_ptr(), of.data_ptr(), ov.data_ptr(),
                                    oseg.ctypes.data, C.byref(n_out), None)
+    else:
+        rc = L.wtamd_runs_coverage_flags(n_seg, seg.ctypes.data, s.data_ptr(), f.data_ptr(), cap, os_.data_ptr(), of.data_ptr(), ov.data_ptr(),
+                                         oseg.ctypes.data, C.byref(n_out), int(flags), None)
     if rc != 0:
         return rc, n_out.value, None
     m = n_out.value
@@ -91,11 +98,12 @@ def _overlap_door(rl, union, capacity=None):
     return 0, m, RunLists(rl.n_chrom, rl.n_tracks, oseg, os_[:m].cpu().numpy(), of[:m].cpu().numpy(), ov[:m].cpu().numpy(), d, rl.chrom_names)
 
 
-def coverage_runlists(rl: RunLists):
+def coverage_runlists(rl: RunLists, any_order=False):
     """The reference's `coverage` (CoverageWiggleIterator, unaryOps.c:303-375) over every track of `rl`, whose intervals may
     overlap (each segment sorted by start), on device (wtamd_runs_coverage): the depth tracks as a new RunLists, f64 values,
-    defaults 0.  Without the reference's one run of start == finish per stream (include/wiggletools_amd.h)."""
-    rc, _, out = _overlap_door(rl, False)
+    defaults 0.  Without the reference's one run of start == finish per stream (include/wiggletools_amd.h).  any_order: the
+    intervals of a segment in any order (wtamd_runs_coverage_flags, WTAMD_COVER_ANY_ORDER)."""
+    rc, _, out = _overlap_door(rl, False, flags=COVER_ANY_ORDER if any_order else None)
     _lib.check(rc)
     return out
 
